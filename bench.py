@@ -5,12 +5,18 @@ LUFS, 4x true peak and the meter aggregates. One process per 
 across ranks (weak scaling) and each step's per-frame outputs are gathered to rank 0 over RCCL
 (overlapped with the next step). Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, this process starts the N rank processes
-itself (before touching any GPU) and exits with their status. Every run also measures cfg4's per-GPU
-shard (4096 stereo frames per GPU = BASELINE cfg4's 32768 at N = 8) as the `cfg4` object.
+itself (before touching any GPU) and exits with their status.
+
+A plain run does what the headline figure needs and nothing else: set-up, W untimed steps, K timed
+steps, the result line. --dump-outputs DIR also writes what the last timed step computed as
+DIR/<name>.npy. --full adds every other measurement to the line: the CPU baselines, cfg4's per-GPU
+shard (4096 stereo frames per GPU = BASELINE cfg4's 32768 at N = 8) as the `cfg4` object, the
+rotating-input and meters-in-call variants, the batch kernel's roofline, cfg5, and at N = 1 the
+cfg3 / cfg1 / latency / drums / app_post lines (each with its own --no-* switch).
 """
 import argparse
 import importlib
@@ -54,6 +60,11 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no-gather", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (rank 0: every rank's, as gathered) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baselines, cfg4, the cfg2 variants, the roofline, cfg5 and the side "
+                         "lines (the --no-* switches below apply to this mode)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline budget (rank 0, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-procs", type=int, default=min(16, os.cpu_count() or 1),
@@ -197,7 +208,7 @@ def measure(be, rank, world, frames, steps, warmup, gather, seed_base=None, prep
     """Time `steps` passes of the hot path over this rank's batch of `frames` stereo frames (after
     `warmup` untimed ones), each step's packed outputs gathered to rank 0 asynchronously
     (double-buffered: step i waits only for the gather of step i - 2). Returns (max-over-ranks
-    seconds, rank 0's last gathered blocks or None, layout)."""
+    seconds, rank 0's last gathered blocks or None, layout, this rank's last packed block)."""
     from omega_gpu import dist as D
     x, lay, bufs, recv = prep if prep is not None else prepare(be, rank, world, frames, seed_base)
     # x: one resident batch, or a list of distinct batches rotated per step (the cache-cold variant)
@@ -256,7 +267,7 @@ def measure(be, rank, world, frames, steps, warmup, gather, seed_base=None, prep
         dt = float(tt.item())
     last = (warmup + steps - 1) % 2
     got = recv[last] if (gather and rank == 0) else None
-    return dt, got, lay
+    return dt, got, lay, bufs[last]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -634,6 +645,16 @@ def warm_clock(fn, seconds=0.1):
         torch.cuda.synchronize()
 
 
+def dump_outputs(path, blocks, lay):
+    """The last timed step's outputs as a caller of the path receives them, <path>/<name>.npy: combined
+    f32[ncf, T], lufs_inst f32[ncf], true_peak_db f32[ncf], meters f64[ncf, 5] -- rank 0's own packed
+    block, or at N > 1 every rank's in rank order as gathered (1.1 MB per GPU at the cfg2 batch)."""
+    os.makedirs(path, exist_ok=True)
+    views = [lay.views(b.cpu()) for b in blocks]
+    for k in views[0]:
+        np.save(os.path.join(path, k + ".npy"), torch.cat([v[k] for v in views]).numpy())
+
+
 def kernel_traffic(kind="batch"):
     """HBM bytes per launch of the dominant kernel from the newest committed counter passes
     (profiles/rNN_<kind>_traffic.json, written by tools/profile_round.sh + tools/summarize_round.py),
@@ -741,6 +762,9 @@ def main(argv=None):
     if world != a.gpus:
         raise SystemExit(f"bench.py: WORLD_SIZE={world} but --gpus {a.gpus}")
     standin = a.standin is not None
+    if not a.full:
+        # a plain run: the headline alone
+        a.no_cpu_baseline = a.no_cfg3 = a.no_cfg4 = a.no_rotating = a.no_cfg5 = True
     cpu_all = None
     if world == 1 and not a.no_cpu_baseline and a.cpu_procs > 1 and not standin:
         # before any GPU call: the workers are forked from this process
@@ -765,7 +789,7 @@ def main(argv=None):
     # headline's K steps are timed at the clock the path runs at in continuous service.
     cfg4 = None
     if not standin and not a.no_cfg4:
-        dt4, _, _ = measure(be, rank, world, FRAMES_CFG4, a.cfg4_steps, 3, gather)
+        dt4, _, _, _ = measure(be, rank, world, FRAMES_CFG4, a.cfg4_steps, 3, gather)
         ncf4 = FRAMES_CFG4 * C
         cfg4 = {"workload": f"cfg4 per-GPU shard: {FRAMES_CFG4} stereo frames x 16384 per GPU "
                             f"({FRAMES_CFG4 * world} stereo frames over {world} GPU(s); BASELINE cfg4 = 32768 "
@@ -775,11 +799,17 @@ def main(argv=None):
                 "value": ncf4 * world * a.cfg4_steps / dt4, "unit": "channel-frames/s",
                 "ms_per_step": dt4 / a.cfg4_steps * 1e3, "steps": a.cfg4_steps,
                 "channel_frames_per_gpu": ncf4, "global_stereo_frames": FRAMES_CFG4 * world}
-    dt, got, lay = measure(be, rank, world, frames, a.steps, a.warmup, gather, prep=prep_main)
+    elif not standin and not a.full:
+        # a plain run: the same ramp out of idle with the headline's own step, untimed
+        be.reset()
+        warm_clock(lambda: be.process(prep_main[0], frames, prep_main[1].views(prep_main[2][0])), 0.05)
+    dt, got, lay, mine = measure(be, rank, world, frames, a.steps, a.warmup, gather, prep=prep_main)
     ncf = frames * C
     value = ncf * world * a.steps / dt
     if a.dump and rank == 0 and got is not None:
         np.save(a.dump, torch.stack([g.cpu() for g in got]).numpy())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, got if got is not None else [mine], lay)
 
     rotating = None
     if not standin and not a.no_rotating:
@@ -789,7 +819,7 @@ def main(argv=None):
         x0 = prep_main[0]
         xr = [x0] + [x0 * (1.0 + 0.0625 * k) for k in range(1, 8)]
         # (800 untimed steps, ~55 ms: the clock back at the continuous-load level after building xr)
-        dtr, _, _ = measure(be, rank, world, frames, a.steps, max(a.warmup, 800), gather,
+        dtr, _, _, _ = measure(be, rank, world, frames, a.steps, max(a.warmup, 800), gather,
                             prep=(xr,) + tuple(prep_main[1:]))
         rotating = {"workload": f"cfg2 step over 8 distinct resident input batches rotated per step "
                                 f"({8 * frames * C * W * 4 / 2**20:.0f} MiB > the 256 MiB Infinity Cache)",
@@ -801,7 +831,7 @@ def main(argv=None):
         # the same step with every call completing its own meter aggregates (no pipelining: the
         # contract of the drop-in facades), on the headline's input
         be.pipelined = False
-        dti, _, _ = measure(be, rank, world, frames, a.steps, max(a.warmup, 400), gather, prep=prep_main)
+        dti, _, _, _ = measure(be, rank, world, frames, a.steps, max(a.warmup, 400), gather, prep=prep_main)
         be.pipelined = True
         be.reset()
         in_call = {"workload": "cfg2 step with each call's meter aggregates computed in its own launch "
@@ -809,7 +839,7 @@ def main(argv=None):
                    "value": frames * C * world * a.steps / dti, "unit": "channel-frames/s",
                    "ms_per_step": dti / a.steps * 1e3}
     roof = None
-    if not standin:
+    if not standin and a.full:
         # (right after the headline, on its input: no idle in between, see above)
         kt_ms, kcf = kernel_time_ms(be.eng, prep_main[0])
         flop_launch = (FLOP_FFT + FLOP_KW + FLOP_TP) * kcf

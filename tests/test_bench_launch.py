@@ -82,6 +82,35 @@ def test_bench_gpus2_pipelined_meters_over_steps(tmp_path):
             np.testing.assert_array_equal(g[k][2 * rank:2 * rank + 2].numpy(), ref[k].numpy(), err_msg=k)
 
 
+def test_bench_dump_outputs_writes_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the outputs of the last timed step (here step 3 of one meter stream: one
+    warmup + two timed) as DIR/<name>.npy in float32 / float64, equal to a single-process oracle run of
+    the same seeded input; the line of a plain run carries ms_per_step and none of the --full objects."""
+    from tests.bench_standin import Backend
+    out = tmp_path / "outputs"
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "1", "--standin", "tests.bench_standin",
+              "--dump-outputs", str(out)], tmp_path)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["cpu_baseline_all_cores"] is None
+    assert not {"cfg4", "cfg5", "cfg3", "cfg1", "latency", "cfg2_rotating_inputs"} & set(line)
+    lay = D.PackedLayout(2, T)
+    be = Backend(0)
+    x = be.input(1, 0, 1)
+    be.reset()
+    for _ in range(3):
+        buf = lay.alloc()
+        be.process(x, 1, lay.views(buf))
+    be.flush()
+    ref = lay.views(buf)
+    assert sorted(os.listdir(out)) == sorted(k + ".npy" for k in ref)
+    for k in ref:
+        got = np.load(out / (k + ".npy"))
+        assert got.dtype == (np.float64 if k == "meters" else np.float32), k
+        np.testing.assert_array_equal(got, ref[k].numpy(), err_msg=k)
+
+
 def test_bench_rejects_world_mismatch(tmp_path):
     r = _run(["--gpus", "2", "--standin", "tests.bench_standin"], tmp_path,
              {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

@@ -3,7 +3,7 @@
 
   rNN_bench.json              the bench line of that run
   rNN_bench_kernel_stats.csv  rocprofv3 --kernel-trace --stats of the driver's bench command
-                              (`bench.py --gpus 1 --steps 20 --warmup 5`, without the CPU baseline)
+                              (`bench.py --full --gpus 1 --steps 20 --warmup 5`, without the CPU baseline)
   rNN_bench_dispatches.md     per-kernel dispatch averages; the true-peak dispatches split into the
                               in-pipeline ones (overlapped with the other streams) and the roofline
                               probe's back-to-back ones (what bench.py's roofline.kernel_ms times)
@@ -40,7 +40,7 @@ def main(rnd):
     per = {}
     for r in rows:
         per.setdefault(short(r["Kernel_Name"]), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-    lines = [f"# Round {rnd}: kernel dispatches of `python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline`",
+    lines = [f"# Round {rnd}: kernel dispatches of `python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline`",
              "", "Source: rocprofv3 --kernel-trace --stats (r%s_bench_kernel_stats.csv); durations in us." % rnd, "",
              "| kernel | dispatches | avg | min | max |", "|---|---|---|---|---|"]
     for k, v in sorted(per.items(), key=lambda kv: -sum(kv[1])):
