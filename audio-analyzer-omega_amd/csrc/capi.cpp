@@ -51,6 +51,7 @@ hipError_t launch_vu(const VuParams& p, hipStream_t s);
 hipError_t launch_transients(const TransientParams& p, hipStream_t s);
 hipError_t launch_transients_any(const TransientParams& p, hipStream_t s);
 hipError_t launch_post(const PostParams& p, hipStream_t s);
+hipError_t launch_pitch(const PitchParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -148,6 +149,29 @@ BiquadCoef butter2_highpass(double fc, double fs) {
   c.a[1] = 2.0 * (K * K - 1.0) / n;
   c.a[2] = (1.0 - std::sqrt(2.0) * K + K * K) / n;
   return c;
+}
+
+// scipy.signal.butter(4, fc/(fs/2), 'high', output='sos'): the analog prototype's pole pairs at angles
+// pi/8 and 3 pi/8 from the negative real axis (Q = 1 / (2 cos)), each through lp2hp and the prewarped
+// bilinear transform: b = (1, -2, 1) / n, a = (1, 2 (K^2 - 1) / n, (1 - K / Q + K^2) / n), n = 1 + K / Q + K^2.
+// zpk2sos orders the sections by pole radius (the pair nearest the unit circle, 3 pi/8, last) and
+// puts the whole gain on the first.
+void butter4_highpass_sos(double fc, double fs, BiquadCoef out[2]) {
+  const double K = std::tan(kPi * fc / fs);
+  double gain = 1.0;
+  for (int s = 0; s < 2; ++s) {
+    const double iq = 2.0 * std::cos(kPi * (s == 0 ? 1.0 : 3.0) / 8.0);  // 1 / Q
+    const double n = 1.0 + K * iq + K * K;
+    gain /= n;
+    BiquadCoef& c = out[s];
+    c.b[0] = 1.0;
+    c.b[1] = -2.0;
+    c.b[2] = 1.0;
+    c.a[0] = 1.0;
+    c.a[1] = 2.0 * (K * K - 1.0) / n;
+    c.a[2] = (1.0 - K * iq + K * K) / n;
+  }
+  for (double& b : out[0].b) b *= gain;
 }
 
 void mat2_mul(const double* A, const double* B, double* C) {
@@ -338,6 +362,11 @@ struct omega_ctx {
   int64_t tr_scratch_cap = 0;
   double* d_sg = nullptr;
   int64_t dflux_cap = 0;  // (elements)
+  // pitch detection (omega_pitch_configure / omega_pitch_detect): the configuration with its derived
+  // periods and high-pass sections, and per frame length the twiddle table and np.hanning window
+  bool pitch_set = false;
+  PitchParams pitch{};
+  std::map<int, std::pair<double2*, double*>> pitch_tabs;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables
@@ -1459,7 +1488,7 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
 
 extern "C" {
 
-const char* omega_version(void) { return "omega-mi355x 0.3 (gfx950, ABI 3)"; }
+const char* omega_version(void) { return "omega-mi355x 0.4 (gfx950, ABI 4)"; }
 
 #ifdef OMEGA_STAMPS
 // Development build only (make dev): one kernel variant over n_cf channel-frames of the context's
@@ -1766,6 +1795,127 @@ int omega_transients(omega_ctx* c, const void* x, int32_t f64, int64_t n_frames,
       q.out = dout + f0 * kTransientCols;
       HIPC(c, launch_transients_any(q, c->stream));
     }
+  }
+  if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+void omega_pitch_config_default(omega_pitch_config* cfg) {
+  if (!cfg) return;
+  // PitchDetectionConfig's defaults at 48 kHz after adjust_for_sample_rate (pitch_detection_config.py:13-121)
+  *cfg = omega_pitch_config{};
+  cfg->sample_rate = 48000;
+  cfg->min_pitch = 50.0;
+  cfg->max_pitch = 2000.0;
+  cfg->yin_threshold = 0.15;
+  cfg->yin_window_size = 1920;
+  cfg->enable_preprocessing = 1;
+  cfg->highpass_frequency = 80.0;
+  cfg->highpass_order = 4;
+  cfg->enable_compression = 1;
+  cfg->compression_threshold = 0.1;
+  cfg->compression_ratio = 0.5;
+}
+
+int omega_pitch_configure(omega_ctx* c, const omega_pitch_config* cfg) try {
+  if (!c || !cfg) return OMEGA_EINVAL;
+  if (cfg->sample_rate <= 0 || !(cfg->min_pitch > 0.0) || !(cfg->max_pitch > cfg->min_pitch))
+    return fail(c, OMEGA_EINVAL, "pitch: need sample_rate > 0 and 0 < min_pitch < max_pitch");
+  if (!(cfg->yin_threshold > 0.0 && cfg->yin_threshold < 1.0) || cfg->yin_window_size <= 0)
+    return fail(c, OMEGA_EINVAL, "pitch: need 0 < yin_threshold < 1 and yin_window_size > 0");
+  const int min_period = (int)(cfg->sample_rate / cfg->max_pitch), max_period = (int)(cfg->sample_rate / cfg->min_pitch);
+  if (min_period < 1) return fail(c, OMEGA_EINVAL, "pitch: max_pitch %g above the sample rate", cfg->max_pitch);
+  PitchParams p{};
+  if (cfg->enable_preprocessing) {
+    if (!(cfg->highpass_frequency > 0.0) || !(cfg->highpass_frequency < cfg->sample_rate / 2.0))
+      return fail(c, OMEGA_EINVAL, "pitch: high-pass frequency %g outside (0, fs/2)", cfg->highpass_frequency);
+    if (cfg->highpass_order != 4)
+      return fail(c, OMEGA_EUNSUP, "pitch: high-pass order %d (every preset's order 4 is built)", cfg->highpass_order);
+    BiquadCoef sos[2];
+    butter4_highpass_sos(cfg->highpass_frequency, cfg->sample_rate, sos);
+    for (int s = 0; s < 2; ++s) {
+      W64Stage& q = p.hp[s];
+      q.b0 = sos[s].b[0], q.b1 = sos[s].b[1], q.b2 = sos[s].b[2];
+      q.a1 = sos[s].a[1], q.a2 = sos[s].a[2];
+    }
+  }
+  p.fs = cfg->sample_rate;
+  p.min_pitch = cfg->min_pitch;
+  p.max_pitch = cfg->max_pitch;
+  p.min_period = min_period;
+  p.max_period = max_period;
+  p.yin_threshold = cfg->yin_threshold;
+  p.yin_window = cfg->yin_window_size;
+  p.preprocess = cfg->enable_preprocessing ? 1 : 0;
+  p.compress = cfg->enable_compression ? 1 : 0;
+  p.comp_threshold = cfg->compression_threshold;
+  p.comp_ratio = cfg->compression_ratio;
+  c->pitch = p;
+  c->pitch_set = true;
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_pitch_detect(omega_ctx* c, const void* x, int32_t f64, int64_t n_frames, int32_t n, int64_t frame_stride,
+                       double* out, int mem) try {
+  if (!c || !out) return OMEGA_EINVAL;
+  if (!c->pitch_set) return fail(c, OMEGA_EINVAL, "pitch: omega_pitch_configure has not been called");
+  if (!x || n_frames < 0 || n <= 0 || frame_stride < 1) return fail(c, OMEGA_EINVAL, "pitch: bad frame layout");
+  if (n_frames == 0) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  if (n < c->pitch.yin_window) {  // detect_pitch_advanced's all-zero result (:487-495)
+    if (mem == OMEGA_MEM_HOST) {
+      std::memset(out, 0, (size_t)n_frames * kPitchCols * sizeof(double));
+      return 0;
+    }
+    HIPC(c, hipMemsetAsync(out, 0, (size_t)n_frames * kPitchCols * sizeof(double), c->stream));
+    return 0;
+  }
+  if (n != 2048 && n != 4096 && n != 8192)
+    return fail(c, OMEGA_EUNSUP, "pitch: frame length %d (2048, 4096 and 8192 are built)", n);
+  auto it = c->pitch_tabs.find(n);
+  if (it == c->pitch_tabs.end()) {
+    std::vector<double2> tw(n + 1);
+    for (int q = 0; q <= n; ++q) tw[q] = make_double2(std::cos(kPi * q / n), -std::sin(kPi * q / n));
+    std::vector<double> win(n);  // np.hanning: 0.5 + 0.5 cos(pi k / (n - 1)), k = 1 - n, 3 - n, ..., n - 1
+    for (int i = 0; i < n; ++i) win[i] = 0.5 + 0.5 * std::cos(kPi * (double)(1 - n + 2 * i) / (n - 1));
+    double2* d1 = nullptr;
+    double* d2 = nullptr;
+    int e = upload(c, &d1, tw);
+    if (!e) e = upload(c, &d2, win);
+    if (e) return e;
+    it = c->pitch_tabs.emplace(n, std::make_pair(d1, d2)).first;
+  }
+  std::vector<HostOut> outs;
+  const void* dx = x;
+  double* dout = out;
+  if (mem == OMEGA_MEM_HOST) {
+    const size_t el = f64 ? 8 : 4;
+    int e = stage_in(c, 0, x, (size_t)((n_frames - 1) * frame_stride + n) * el, &dx);
+    if (!e) e = stage_out(c, 1, out, (size_t)n_frames * kPitchCols, outs, &dout);
+    if (e) return e;
+  }
+  PitchParams p = c->pitch;
+  p.x = dx;
+  p.f64 = f64 ? 1 : 0;
+  p.n_frames = n_frames;
+  p.n = n;
+  p.frame_stride = frame_stride;
+  p.tw = it->second.first;
+  p.win = it->second.second;
+  p.out = dout;
+  // one launch covers at most 2^30 workgroups (three per frame)
+  const int64_t per = (int64_t)1 << 28;
+  const size_t el = f64 ? 8 : 4;
+  for (int64_t f0 = 0; f0 < n_frames; f0 += per) {
+    PitchParams q = p;
+    q.x = static_cast<const char*>(dx) + (size_t)(f0 * frame_stride) * el;
+    q.n_frames = std::min(per, n_frames - f0);
+    q.out = dout + f0 * kPitchCols;
+    HIPC(c, launch_pitch(q, c->stream));
   }
   if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
   return 0;

@@ -449,6 +449,28 @@ struct Weight64Params {
   float* lufs_out;          // [n] or nullptr
 };
 
+// CepstralAnalyzer.detect_pitch_advanced (pitch.hip; omega4/panels/pitch_detection.py:21-611): three
+// workgroup roles per frame (cepstrum, autocorrelation, YIN) and a per-frame combine
+constexpr int kPitchCols = 10;  // pitch, confidence, cepstral / autocorrelation / YIN (pitch, confidence), rms, flags
+constexpr int kPitchThreads = 256;
+struct PitchParams {
+  const void* x;            // frame f at x + f * frame_stride (float32, or float64 when f64)
+  int f64;
+  int64_t n_frames;
+  int n;                    // 2048, 4096 or 8192
+  int64_t frame_stride;
+  double fs, min_pitch, max_pitch;
+  int min_period, max_period;
+  double yin_threshold;
+  int yin_window;           // <= n
+  int preprocess, compress;
+  double comp_threshold, comp_ratio;
+  W64Stage hp[2];           // the order-4 high-pass as two DF2T sections (b0, b1, b2, a1, a2)
+  const double2* tw;        // [n + 1] e^{-2 pi i q / (2 n)}
+  const double* win;        // [n] np.hanning(n)
+  double* out;              // [n_frames, kPitchCols]
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

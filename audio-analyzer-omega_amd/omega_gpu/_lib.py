@@ -48,6 +48,13 @@ class IngestStats(C.Structure):
                 ("frames_polled", C.c_int64), ("dropped_frames", C.c_int64)]
 
 
+class PitchConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("min_pitch", C.c_double), ("max_pitch", C.c_double),
+                ("yin_threshold", C.c_double), ("yin_window_size", C.c_int32), ("enable_preprocessing", C.c_int32),
+                ("highpass_frequency", C.c_double), ("highpass_order", C.c_int32), ("enable_compression", C.c_int32),
+                ("compression_threshold", C.c_double), ("compression_ratio", C.c_double)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -80,6 +87,10 @@ EXPORTS = {
     "omega_vu_reset": (C.c_int, [C.c_void_p]),
     "omega_transients": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
                                    C.c_int]),
+    "omega_pitch_config_default": (None, [C.POINTER(PitchConfig)]),
+    "omega_pitch_configure": (C.c_int, [C.c_void_p, C.POINTER(PitchConfig)]),
+    "omega_pitch_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                     C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

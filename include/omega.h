@@ -35,6 +35,7 @@
  *   omega_ingest_*         capture chunks -> ring -> analysis          omega4/audio/capture.py:512-600,
  *                          omega4_main.py:648-688 (§8(f) row 3)
  *   omega_transients       TransientAnalyzer.analyze_transients        omega4/analyzers/transient.py:19-108 (§8(f) row 4)
+ *   omega_pitch_*          CepstralAnalyzer.detect_pitch_advanced      omega4/panels/pitch_detection.py:21-611 (§8(f) row 5)
  *
  * Conventions:
  *   - every function returns 0 on success and a negative omega_status on error; the message is
@@ -59,7 +60,7 @@
 extern "C" {
 #endif
 
-#define OMEGA_ABI_VERSION 3
+#define OMEGA_ABI_VERSION 4
 #define OMEGA_MAX_RES 4
 #define OMEGA_N_METERS 5 /* momentary, short_term, integrated, range, true_peak */
 
@@ -346,6 +347,43 @@ int omega_vu_reset(omega_ctx* ctx);
  * envelope's mean (the value the reference appends to its envelope_history). */
 int omega_transients(omega_ctx* ctx, const void* x, int32_t f64, int64_t n_frames, int32_t n, int64_t frame_stride,
                      double* out, int mem);
+
+/* CepstralAnalyzer.detect_pitch_advanced (omega4/panels/pitch_detection.py:485-556; ABI 4) for n_frames
+ * frames of n samples (2048, 4096 or 8192; float32, or float64 when f64 != 0 -- cast to float32 on load
+ * as :587-588 does), frame f at x + f*frame_stride (frame_stride may be smaller than n: an overlapping
+ * stream). Three methods per frame and their confidence-weighted combination:
+ *   cepstrum         float64: order-4 Butterworth high-pass (sosfilt, zero state) + RMS compression
+ *                    (:497-525), Hann window, rfft, log(|X| + 1e-10), irfft (:132-144), the strongest
+ *                    find_peaks peak of the period range (:146-174)
+ *   autocorrelation  x - mean, zero-padded to 2n, irfft(|rfft|^2) / (r[0] + 1e-10) (:176-195), the first
+ *                    peak find_peaks(height=0.3, distance=20) keeps (:197-227)
+ *   YIN              the vectorised path over the first yin_window_size samples (:229-316, :363-371)
+ *   combine          :373-433 with the acceptance thresholds 0.15 / 0.2 / 0.25 and the weights 0.8 / 0.9 /
+ *                    1.1 the reference hard-codes (it does not read its config's *_weight fields)
+ * omega_pitch_configure designs the high-pass sections (scipy.signal.butter's closed form; order 4, the
+ * order of every reference preset -- other orders return OMEGA_EUNSUP) and stores the settings; it must
+ * precede omega_pitch_detect. out [n_frames, 10] float64: pitch, confidence, cepstral pitch and
+ * confidence, autocorrelation pitch and confidence, YIN pitch and confidence, the frame's RMS, flags
+ * (bit 0: non-finite samples, bit 1: RMS below 1e-6 -- validate_audio_input :79-91). A flagged frame's
+ * first eight columns are zero; it does not affect the other frames of the batch. n < yin_window_size
+ * gives the reference's all-zero result (:487-495); any other n outside {2048, 4096, 8192} returns
+ * OMEGA_EUNSUP. The note name, stability and histories (:435-483) are scalar host work left to the caller. */
+typedef struct {
+  int32_t sample_rate;
+  double min_pitch, max_pitch;       /* Hz; periods int(fs / max_pitch) .. int(fs / min_pitch) */
+  double yin_threshold;
+  int32_t yin_window_size;           /* after PitchDetectionConfig.adjust_for_sample_rate */
+  int32_t enable_preprocessing;
+  double highpass_frequency;
+  int32_t highpass_order;            /* 4 */
+  int32_t enable_compression;
+  double compression_threshold, compression_ratio;
+} omega_pitch_config;
+/* PitchDetectionConfig's defaults at 48 kHz (pitch_detection_config.py:13-121): 50..2000 Hz, window 1920. */
+void omega_pitch_config_default(omega_pitch_config* cfg);
+int omega_pitch_configure(omega_ctx* ctx, const omega_pitch_config* cfg);
+int omega_pitch_detect(omega_ctx* ctx, const void* x, int32_t f64, int64_t n_frames, int32_t n, int64_t frame_stride,
+                       double* out, int mem);
 
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks

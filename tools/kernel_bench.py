@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Run one stage of the cfg2 hot path in isolation (for rocprofv3 counter passes and A/B timing).
 
-  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post} [--reps N]
+  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch} [--reps N]
 
 spectra-bands / spectra-chroma / spectra-mag: the cfg3 kernel with one output set only (where its LDS
 bank conflicts and time come from); spectra-rot: bench.py's cfg3 call, rotating over 4 distinct input
@@ -69,6 +69,17 @@ def main():
         px = torch.from_numpy(rng.random((4096, 512)).astype(np.float32)).cuda()
         pp = SpectrumPostProcessor(np.linspace(20, 20000, 512))
 
+    if a.stage == "pitch":  # CepstralAnalyzer over 4096 resident frames x 4096 samples (balanced preset)
+        from omega_gpu.pitch_detection import CepstralAnalyzer
+        rng = np.random.default_rng(7)
+        tt = np.arange(4096) / 48000.0
+        f0 = rng.uniform(60.0, 1800.0, 4096)[:, None]
+        px = sum((0.7 ** k) * np.sin(2 * np.pi * f0 * (k + 1) * tt[None, :]) for k in range(4))
+        px = torch.from_numpy((0.2 * px + 0.01 * rng.standard_normal(px.shape)).astype(np.float32)).cuda()
+        pan = CepstralAnalyzer(48000)
+        pout = torch.empty(4096, 10, dtype=torch.float64, device="cuda")
+        pan._eng._bind_stream(px)
+
     outs = L.Outputs()
     outs.combined, outs.lufs_inst, outs.true_peak_db = comb.data_ptr(), out["li"].data_ptr(), out["tp"].data_ptr()
 
@@ -104,6 +115,9 @@ def main():
             deng.drum_features(dmag, out=dout)
         if a.stage == "post":
             pp.process(px)
+        if a.stage == "pitch":
+            pan._eng._check(lib.omega_pitch_detect(pan._eng._ctx, px.data_ptr(), 0, 4096, 4096, 4096, pout.data_ptr(),
+                                                   L.MEM_DEVICE))
         if a.stage == "host":  # host buffers in and out: PCIe-inclusive rate of the full path
             host_out.update(eng.process_frames(xh, 256, 2 * 16384, 16384, meters=True))
         if a.stage in ("tp", "all"):
@@ -129,6 +143,9 @@ def main():
     t_end = time.time()
     us = s.elapsed_time(e) / a.reps * 1e3
     print(f"window {t_begin:.3f} {t_end:.3f}")
+    if a.stage == "pitch":
+        print(f"pitch: {us:.1f} us per call of 4096 frames = {4096 / us * 1e6:.0f} frames/s ({us / 4096:.3f} us per frame)")
+        return
     print(f"{a.stage}: {us:.1f} us per call, {us * 1e3 / ncf:.1f} ns per channel-frame ({ncf} cf)" +
           (f" = {ncf / us * 1e6:.0f} channel-frames/s (host in/out)" if a.stage == "host" else ""))
 
