@@ -52,6 +52,7 @@ hipError_t launch_transients(const TransientParams& p, hipStream_t s);
 hipError_t launch_transients_any(const TransientParams& p, hipStream_t s);
 hipError_t launch_post(const PostParams& p, hipStream_t s);
 hipError_t launch_pitch(const PitchParams& p, hipStream_t s);
+hipError_t launch_harmonic(const HarmonicParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -367,6 +368,15 @@ struct omega_ctx {
   bool pitch_set = false;
   PitchParams pitch{};
   std::map<int, std::pair<double2*, double*>> pitch_tabs;
+  // harmonic analysis (omega_harmonic_configure / omega_harmonic_analyze): the configuration, the
+  // frequency table, the previous frame's spectrum (double-buffered: a launch reads one and writes the
+  // other) and np.hamming per audio length
+  bool harm_set = false, harm_has_prev = false;
+  HarmonicParams harm{};
+  double* d_hfreqs = nullptr;
+  float* d_hprev[2] = {};
+  int harm_cur = 0;
+  std::map<int, double*> harm_ham;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables
@@ -1488,7 +1498,7 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
 
 extern "C" {
 
-const char* omega_version(void) { return "omega-mi355x 0.4 (gfx950, ABI 4)"; }
+const char* omega_version(void) { return "omega-mi355x 0.5 (gfx950, ABI 5)"; }
 
 #ifdef OMEGA_STAMPS
 // Development build only (make dev): one kernel variant over n_cf channel-frames of the context's
@@ -1917,6 +1927,200 @@ int omega_pitch_detect(omega_ctx* c, const void* x, int32_t f64, int64_t n_frame
     q.out = dout + f0 * kPitchCols;
     HIPC(c, launch_pitch(q, c->stream));
   }
+  if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+void omega_harmonic_config_default(omega_harmonic_config* cfg) {
+  if (!cfg) return;
+  *cfg = omega_harmonic_config{};
+  cfg->sample_rate = 48000;
+  cfg->n_bins = 512;
+  cfg->max_series = 16;
+}
+
+int omega_harmonic_configure(omega_ctx* c, const omega_harmonic_config* cfg, const double* freqs) try {
+  if (!c || !cfg) return OMEGA_EINVAL;
+  if (!freqs) return fail(c, OMEGA_EINVAL, "harmonic: freqs is NULL");
+  if (cfg->sample_rate <= 0) return fail(c, OMEGA_EINVAL, "harmonic: need sample_rate > 0");
+  if (cfg->max_series < 1 || cfg->max_series > 1024)
+    return fail(c, OMEGA_EINVAL, "harmonic: max_series %d outside 1..1024", cfg->max_series);
+  if (cfg->n_bins < 2) return fail(c, OMEGA_EINVAL, "harmonic: n_bins %d", cfg->n_bins);
+  if (cfg->n_bins < kHarmonicMinBins || cfg->n_bins > kHarmonicMaxBins)
+    return fail(c, OMEGA_EUNSUP, "harmonic: %d spectrum bins (%d..%d are built)", cfg->n_bins, kHarmonicMinBins,
+                kHarmonicMaxBins);
+  for (int i = 0; i < cfg->n_bins; ++i)
+    if (!std::isfinite(freqs[i]) || (i && !(freqs[i] > freqs[i - 1])))
+      return fail(c, OMEGA_EINVAL, "harmonic: freqs must be finite and strictly increasing (entry %d)", i);
+  HIPC(c, hipSetDevice(c->device));
+  if (c->d_hfreqs) {  // a reconfiguration: work already enqueued may still read the old tables
+    HIPC(c, hipStreamSynchronize(c->stream));
+    for (void* q : {(void*)c->d_hfreqs, (void*)c->d_hprev[0], (void*)c->d_hprev[1]}) {
+      auto it = std::find(c->allocs.begin(), c->allocs.end(), q);
+      if (it != c->allocs.end()) c->allocs.erase(it);
+      if (q) (void)hipFree(q);
+    }
+    c->d_hfreqs = nullptr;
+    c->d_hprev[0] = c->d_hprev[1] = nullptr;
+    c->harm_set = false;
+  }
+  const std::vector<double> tab(freqs, freqs + cfg->n_bins);
+  int e = upload(c, &c->d_hfreqs, tab);
+  for (int b = 0; b < 2 && !e; ++b) e = dalloc(c, &c->d_hprev[b], (size_t)cfg->n_bins);
+  if (e) return e;
+  HarmonicParams p{};
+  p.n_bins = cfg->n_bins;
+  p.freqs = c->d_hfreqs;
+  p.fs = cfg->sample_rate;
+  p.nyquist = cfg->sample_rate / 2.0;
+  p.max_series = cfg->max_series;
+  c->harm = p;
+  c->harm_cur = 0;
+  c->harm_has_prev = false;
+  c->harm_set = true;
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_harmonic_reset(omega_ctx* c) try {
+  if (!c) return OMEGA_EINVAL;
+  c->harm_has_prev = false;
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+namespace {
+// np.hamming(m) on the device, cached per audio length: at most kHarmonicWindows tables (a caller that
+// varies m does not grow device memory; past the cap the cache is emptied once the stream is idle)
+constexpr size_t kHarmonicWindows = 8;
+int harmonic_window(omega_ctx* c, int m, double** out) {
+  auto it = c->harm_ham.find(m);
+  if (it == c->harm_ham.end()) {
+    if (c->harm_ham.size() >= kHarmonicWindows) {
+      HIPC(c, hipStreamSynchronize(c->stream));
+      for (auto& kv : c->harm_ham) {
+        auto a = std::find(c->allocs.begin(), c->allocs.end(), static_cast<void*>(kv.second));
+        if (a != c->allocs.end()) c->allocs.erase(a);
+        (void)hipFree(kv.second);
+      }
+      c->harm_ham.clear();
+    }
+    std::vector<double> win(m);  // np.hamming: 0.54 + 0.46 cos(pi k / (m - 1)), k = 1 - m, 3 - m, ..., m - 1
+    for (int i = 0; i < m; ++i) win[i] = 0.54 + 0.46 * std::cos(kPi * (double)(1 - m + 2 * i) / (m - 1));
+    double* d = nullptr;
+    if (int e = upload(c, &d, win)) return e;
+    it = c->harm_ham.emplace(m, d).first;
+  }
+  *out = it->second;
+  return 0;
+}
+}  // namespace
+
+int omega_harmonic_analyze(omega_ctx* c, const float* spectra, int64_t spec_stride, const void* audio, int32_t f64,
+                           int32_t m, int64_t audio_stride, int64_t n_frames, double* out, int32_t* series_bins,
+                           double* series_strength, int mem) try {
+  if (!c || !out) return OMEGA_EINVAL;
+  if (!c->harm_set) return fail(c, OMEGA_EINVAL, "harmonic: omega_harmonic_configure has not been called");
+  const int K = c->harm.n_bins, S = c->harm.max_series;
+  if (!spectra || n_frames < 0 || spec_stride < 1) return fail(c, OMEGA_EINVAL, "harmonic: bad spectrum layout");
+  if (audio && (m <= 0 || audio_stride < 1)) return fail(c, OMEGA_EINVAL, "harmonic: bad audio layout");
+  if (audio && (m < kHarmonicMinAudio || m > kHarmonicMaxAudio))
+    return fail(c, OMEGA_EUNSUP, "harmonic: %d audio samples per frame (%d..%d are built)", m, kHarmonicMinAudio,
+                kHarmonicMaxAudio);
+  if (n_frames == 0) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  double* dham = nullptr;
+  if (audio)
+    if (int e = harmonic_window(c, m, &dham)) return e;
+  std::vector<HostOut> outs;
+  const float* dspec = spectra;
+  const void* daudio = audio;
+  double* dout = out;
+  int32_t* dbins = series_bins;
+  double* dstr = series_strength;
+  if (mem == OMEGA_MEM_HOST) {
+    const void* q = nullptr;
+    int e = stage_in(c, 0, spectra, (size_t)((n_frames - 1) * spec_stride + K) * sizeof(float), &q);
+    dspec = static_cast<const float*>(q);
+    if (!e && audio) e = stage_in(c, 1, audio, (size_t)((n_frames - 1) * audio_stride + m) * (f64 ? 8 : 4), &daudio);
+    if (!e) e = stage_out(c, 2, out, (size_t)n_frames * kHarmonicCols, outs, &dout);
+    if (!e) e = stage_out(c, 3, series_bins, (size_t)n_frames * S * (1 + kHarmonicMaxHarm), outs, &dbins);
+    if (!e) e = stage_out(c, 4, series_strength, (size_t)n_frames * S, outs, &dstr);
+    if (e) return e;
+  }
+  HarmonicParams p = c->harm;
+  p.spec_stride = spec_stride;
+  p.f64 = f64 ? 1 : 0;
+  p.m = audio ? m : 0;
+  p.audio_stride = audio_stride;
+  p.ham = dham;
+  const int a = c->harm_cur, b = a ^ 1;
+  // one launch covers at most 2^30 workgroups (two per frame)
+  const int64_t per = (int64_t)1 << 29;
+  const size_t el = f64 ? 8 : 4;
+  for (int64_t f0 = 0; f0 < n_frames; f0 += per) {
+    HarmonicParams q = p;
+    q.n_frames = std::min(per, n_frames - f0);
+    q.spec = dspec + f0 * spec_stride;
+    q.audio = daudio ? static_cast<const char*>(daudio) + (size_t)(f0 * audio_stride) * el : nullptr;
+    q.prev_in = f0 ? dspec + (f0 - 1) * spec_stride : (c->harm_has_prev ? c->d_hprev[a] : nullptr);
+    q.prev_out = f0 + q.n_frames == n_frames ? c->d_hprev[b] : nullptr;
+    q.out = dout + f0 * kHarmonicCols;
+    q.series_bins = dbins ? dbins + f0 * S * (1 + kHarmonicMaxHarm) : nullptr;
+    q.series_strength = dstr ? dstr + f0 * S : nullptr;
+    HIPC(c, launch_harmonic(q, c->stream));
+  }
+  c->harm_cur = b;
+  c->harm_has_prev = true;
+  if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_harmonic_metrics(omega_ctx* c, const float* spectrum, const float* previous, const void* audio, int32_t f64,
+                           int32_t m, double fundamental, double* out, int mem) try {
+  if (!c || !out) return OMEGA_EINVAL;
+  if (!c->harm_set) return fail(c, OMEGA_EINVAL, "harmonic: omega_harmonic_configure has not been called");
+  if (!spectrum) return fail(c, OMEGA_EINVAL, "harmonic: spectrum is NULL");
+  if (audio && m <= 0) return fail(c, OMEGA_EINVAL, "harmonic: bad audio layout");
+  if (audio && (m < kHarmonicMinAudio || m > kHarmonicMaxAudio))
+    return fail(c, OMEGA_EUNSUP, "harmonic: %d audio samples per frame (%d..%d are built)", m, kHarmonicMinAudio,
+                kHarmonicMaxAudio);
+  HIPC(c, hipSetDevice(c->device));
+  double* dham = nullptr;
+  if (audio)
+    if (int e = harmonic_window(c, m, &dham)) return e;
+  const int K = c->harm.n_bins;
+  std::vector<HostOut> outs;
+  const void *dspec = spectrum, *dprev = previous, *daudio = audio;
+  double* dout = out;
+  if (mem == OMEGA_MEM_HOST) {
+    int e = stage_in(c, 0, spectrum, (size_t)K * sizeof(float), &dspec);
+    if (!e && audio) e = stage_in(c, 1, audio, (size_t)m * (f64 ? 8 : 4), &daudio);
+    if (!e && previous) e = stage_in(c, 2, previous, (size_t)K * sizeof(float), &dprev);
+    if (!e) e = stage_out(c, 3, out, (size_t)kHarmonicCols, outs, &dout);
+    if (e) return e;
+  }
+  HarmonicParams p = c->harm;  // (the stream state -- the stored previous spectrum -- is neither read nor written)
+  p.spec = static_cast<const float*>(dspec);
+  p.spec_stride = K;
+  p.audio = daudio;
+  p.f64 = f64 ? 1 : 0;
+  p.m = audio ? m : 0;
+  p.audio_stride = m > 0 ? m : 1;
+  p.ham = dham;
+  p.n_frames = 1;
+  p.ungated = 1;
+  p.f0 = fundamental;
+  p.prev_in = static_cast<const float*>(dprev);
+  p.prev_out = nullptr;
+  p.out = dout;
+  HIPC(c, launch_harmonic(p, c->stream));
   if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
   return 0;
 } catch (...) {

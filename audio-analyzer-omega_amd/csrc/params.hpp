@@ -471,6 +471,38 @@ struct PitchParams {
   double* out;              // [n_frames, kPitchCols]
 };
 
+// HarmonicAnalyzer.detect_harmonic_series (harmonic.hip; omega4/panels/harmonic_analysis.py:193-333 and
+// omega4/analyzers/harmonic_metrics.py): two workgroup roles per frame (spectrum side, LPC formants) and
+// a per-frame combine
+constexpr int kHarmonicCols = 16;     // series count, dominant fundamental, thd, thd+n, centroid, spread, flux,
+                                      // rolloff, inharmonicity, hnr, formant count, F1..F4, flags
+constexpr int kHarmonicThreads = 256;
+constexpr int kHarmonicMaxHarm = 16;  // harmonics per series; a series row is the peak bin and these
+constexpr int kHarmonicMinBins = 16, kHarmonicMaxBins = 8193;
+constexpr int kHarmonicMinAudio = 15, kHarmonicMaxAudio = 8192;
+constexpr int kHarmonicLpcOrder = 14;
+struct HarmonicParams {
+  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 magnitudes
+  int64_t spec_stride;
+  int n_bins;
+  const double* freqs;      // [n_bins] strictly increasing
+  const void* audio;        // frame f at audio + f * audio_stride (float32, or float64 when f64); nullptr: none
+  int f64;
+  int m;                    // audio samples per frame
+  int64_t audio_stride;
+  const double* ham;        // [m] np.hamming(m)
+  int64_t n_frames;
+  double fs, nyquist;
+  int max_series;
+  int ungated;              // omega_harmonic_metrics: metrics for f0 and formants whether or not a series is found
+  double f0;                // the caller's fundamental when ungated (<= 0: the f0 metrics are 0)
+  const float* prev_in;     // the spectrum frame 0 compares with, or nullptr (flux 0)
+  float* prev_out;          // [n_bins] the last frame's spectrum, or nullptr (not this launch's last)
+  double* out;              // [n_frames, kHarmonicCols]
+  int* series_bins;         // [n_frames, max_series, 1 + kHarmonicMaxHarm] or nullptr
+  double* series_strength;  // [n_frames, max_series] or nullptr
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

@@ -7,8 +7,10 @@ built library raises ImportError -- there is no CPU fallback.
 from ._lib import LIB_PATH, OmegaError, UnsupportedError, lib
 from .engine import DEFAULT_RESOLUTIONS, METER_KEYS, NORTHSTAR_RESOLUTIONS, BandTable, Engine, Resolution
 from .pitch_detection import CepstralAnalyzer, PitchDetectionConfig, get_preset_config, list_presets
+from .harmonic_analysis import HarmonicAnalyzer, HarmonicMetrics
 
 __all__ = [
+    "HarmonicAnalyzer", "HarmonicMetrics",
     "LIB_PATH", "OmegaError", "UnsupportedError", "lib", "Engine", "Resolution", "BandTable",
     "DEFAULT_RESOLUTIONS", "NORTHSTAR_RESOLUTIONS", "METER_KEYS",
     "CepstralAnalyzer", "PitchDetectionConfig", "get_preset_config", "list_presets",

@@ -55,6 +55,10 @@ class PitchConfig(C.Structure):
                 ("compression_threshold", C.c_double), ("compression_ratio", C.c_double)]
 
 
+class HarmonicConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("n_bins", C.c_int32), ("max_series", C.c_int32)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -91,6 +95,13 @@ EXPORTS = {
     "omega_pitch_configure": (C.c_int, [C.c_void_p, C.POINTER(PitchConfig)]),
     "omega_pitch_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
                                      C.c_int]),
+    "omega_harmonic_config_default": (None, [C.POINTER(HarmonicConfig)]),
+    "omega_harmonic_configure": (C.c_int, [C.c_void_p, C.POINTER(HarmonicConfig), C.c_void_p]),
+    "omega_harmonic_analyze": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "omega_harmonic_reset": (C.c_int, [C.c_void_p]),
+    "omega_harmonic_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_double, C.c_void_p, C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -36,6 +36,9 @@
  *                          omega4_main.py:648-688 (§8(f) row 3)
  *   omega_transients       TransientAnalyzer.analyze_transients        omega4/analyzers/transient.py:19-108 (§8(f) row 4)
  *   omega_pitch_*          CepstralAnalyzer.detect_pitch_advanced      omega4/panels/pitch_detection.py:21-611 (§8(f) row 5)
+ *   omega_harmonic_*       HarmonicAnalyzer.detect_harmonic_series     omega4/panels/harmonic_analysis.py:193-333 with
+ *                          HarmonicMetrics (THD, THD+N, spectral shape, HNR, LPC formants)
+ *                          omega4/analyzers/harmonic_metrics.py:51-357 (§8(f) row 6)
  *
  * Conventions:
  *   - every function returns 0 on success and a negative omega_status on error; the message is
@@ -60,7 +63,7 @@
 extern "C" {
 #endif
 
-#define OMEGA_ABI_VERSION 4
+#define OMEGA_ABI_VERSION 5
 #define OMEGA_MAX_RES 4
 #define OMEGA_N_METERS 5 /* momentary, short_term, integrated, range, true_peak */
 
@@ -384,6 +387,55 @@ void omega_pitch_config_default(omega_pitch_config* cfg);
 int omega_pitch_configure(omega_ctx* ctx, const omega_pitch_config* cfg);
 int omega_pitch_detect(omega_ctx* ctx, const void* x, int32_t f64, int64_t n_frames, int32_t n, int64_t frame_stride,
                        double* out, int mem);
+
+/* HarmonicAnalyzer.detect_harmonic_series (omega4/panels/harmonic_analysis.py:193-333; ABI 5) for
+ * n_frames frames: the float32 spectrum of n_bins magnitudes at spectra + f*spec_stride over the float64
+ * frequency table given to omega_harmonic_configure, and -- optionally -- the frame's m audio samples
+ * (float32, or float64 when f64 != 0; widened to float64 on load) at audio + f*audio_stride for the LPC
+ * formants. audio == NULL is the reference's audio_data=None: no formants.
+ *   peaks      scipy.signal.find_peaks(height = 0.1 max, distance = 10) with scipy's plateau rule (the
+ *              middle of a flat top) and its distance rule over all peaks, highest first
+ *   series     per surviving peak with 20 <= f <= 2000 Hz up to 16 harmonics (:281-333); kept when the
+ *              strength score exceeds 0.3, sorted by strength (descending, stable)
+ *   metrics    for the first series' fundamental: THD, THD+N, centroid, spread, rolloff, flux against the
+ *              previous frame, inharmonicity, HNR (harmonic_metrics.py:51-357); all 0 without a series
+ *   formants   detect_formants_lpc (:115-196): order 14, the reference's recursion as written, the roots
+ *              by a simultaneous iteration; only when a series was found
+ * out [n_frames, 16] float64: series count (the true count, even above max_series), dominant
+ * fundamental, thd, thd_plus_noise, centroid, spread, flux, rolloff, inharmonicity, hnr_db, formant
+ * count, F1..F4, flags (bit 0: the root iteration did not converge -- no formants; bit 1: non-finite
+ * input -- a non-finite spectrum gives the zero row). series_bins [n_frames, max_series, 17] int32: the
+ * peak bin, then the bin of harmonic n = 1..16 or -1 where it was not accepted (rows past the count are
+ * -1); series_strength [n_frames, max_series] float64 in the sorted order. Both may be NULL.
+ * Flux state: frame f compares with frame f-1 of the call, frame 0 with the spectrum the context kept
+ * from the previous call (flux 0 when there is none); the call's last spectrum is kept whether or not it
+ * had a series (a non-finite spectrum too: the next frame's flux leaves its non-finite bins out and that
+ * frame carries flag bit 1). omega_harmonic_reset forgets it; omega_harmonic_configure (which must precede
+ * omega_harmonic_analyze and may be repeated with another table) does too.
+ * Supported: 16 <= n_bins <= 8193, strictly increasing freqs, 15 <= m <= 8192; other sizes return
+ * OMEGA_EUNSUP, a non-increasing table or max_series outside 1..1024 OMEGA_EINVAL. Instrument matching
+ * (:335-431) and the vowel lookup are scalar host work left to the caller. */
+typedef struct {
+  int32_t sample_rate;
+  int32_t n_bins;                    /* entries of freqs and bins per spectrum */
+  int32_t max_series;                /* rows of series_bins / series_strength per frame */
+} omega_harmonic_config;
+/* 48000 Hz, 512 bins (the app's combined spectrum), 16 series. */
+void omega_harmonic_config_default(omega_harmonic_config* cfg);
+int omega_harmonic_configure(omega_ctx* ctx, const omega_harmonic_config* cfg, const double* freqs);
+int omega_harmonic_analyze(omega_ctx* ctx, const float* spectra, int64_t spec_stride, const void* audio, int32_t f64,
+                           int32_t m, int64_t audio_stride, int64_t n_frames, double* out, int32_t* series_bins,
+                           double* series_strength, int mem);
+int omega_harmonic_reset(omega_ctx* ctx);
+/* The HarmonicMetrics methods for ONE frame and a fundamental the caller names (harmonic_metrics.py:51-357),
+ * stateless like the reference's: the same kernels and the same `out` row as omega_harmonic_analyze, but
+ * thd, thd_plus_noise, inharmonicity and hnr_db are evaluated for `fundamental` (all 0 when it is <= 0),
+ * centroid / spread / rolloff and the formants (when audio != NULL) whether or not the spectrum holds a
+ * harmonic series, and the flux against `previous` (n_bins values; NULL: 0). Columns 0 and 1 are the
+ * series count found and `fundamental`. The stream state of omega_harmonic_analyze is neither read nor
+ * written. */
+int omega_harmonic_metrics(omega_ctx* ctx, const float* spectrum, const float* previous, const void* audio,
+                           int32_t f64, int32_t m, double fundamental, double* out, int mem);
 
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Run one stage of the cfg2 hot path in isolation (for rocprofv3 counter passes and A/B timing).
 
-  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch} [--reps N]
+  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic} [--reps N]
 
 spectra-bands / spectra-chroma / spectra-mag: the cfg3 kernel with one output set only (where its LDS
 bank conflicts and time come from); spectra-rot: bench.py's cfg3 call, rotating over 4 distinct input
@@ -80,6 +80,24 @@ def main():
         pout = torch.empty(4096, 10, dtype=torch.float64, device="cuda")
         pan._eng._bind_stream(px)
 
+    if a.stage == "harmonic":  # HarmonicAnalyzer over 4096 resident frames: 512-bin spectra, 2048-sample audio
+        from omega_gpu.harmonic_analysis import HarmonicAnalyzer
+        rng = np.random.default_rng(8)
+        hfr = np.linspace(0, 24000, 512)
+        tt = np.arange(2048) / 48000.0
+        f0 = hfr[rng.integers(3, 40, 4096)][:, None]
+        hx = sum((1.0 / (k + 1)) * np.sin(2 * np.pi * f0 * (k + 1) * tt[None, :]) for k in range(8))
+        hx = (0.3 * hx + 0.002 * rng.standard_normal(hx.shape)) * np.hanning(2048)
+        hs = np.abs(np.fft.rfft(hx[:, :1022] * np.hanning(1022), axis=1))
+        hs = torch.from_numpy(np.minimum(1.6 * (hs / hs.max(axis=1, keepdims=True)) ** 0.7, 1.0).astype(np.float32)).cuda()
+        hx = torch.from_numpy(hx).cuda()
+        han = HarmonicAnalyzer(48000)
+        han.analyze_frames(hs[:1], hfr, hx[:1])  # (configures the table)
+        hout = torch.empty(4096, 16, dtype=torch.float64, device="cuda")
+        hsb = torch.empty(4096, 16, 17, dtype=torch.int32, device="cuda")
+        hss = torch.empty(4096, 16, dtype=torch.float64, device="cuda")
+        han._eng._bind_stream(hs)
+
     outs = L.Outputs()
     outs.combined, outs.lufs_inst, outs.true_peak_db = comb.data_ptr(), out["li"].data_ptr(), out["tp"].data_ptr()
 
@@ -118,6 +136,9 @@ def main():
         if a.stage == "pitch":
             pan._eng._check(lib.omega_pitch_detect(pan._eng._ctx, px.data_ptr(), 0, 4096, 4096, 4096, pout.data_ptr(),
                                                    L.MEM_DEVICE))
+        if a.stage == "harmonic":
+            han._eng._check(lib.omega_harmonic_analyze(han._eng._ctx, hs.data_ptr(), 512, hx.data_ptr(), 1, 2048, 2048,
+                                                       4096, hout.data_ptr(), hsb.data_ptr(), hss.data_ptr(), L.MEM_DEVICE))
         if a.stage == "host":  # host buffers in and out: PCIe-inclusive rate of the full path
             host_out.update(eng.process_frames(xh, 256, 2 * 16384, 16384, meters=True))
         if a.stage in ("tp", "all"):
@@ -145,6 +166,9 @@ def main():
     print(f"window {t_begin:.3f} {t_end:.3f}")
     if a.stage == "pitch":
         print(f"pitch: {us:.1f} us per call of 4096 frames = {4096 / us * 1e6:.0f} frames/s ({us / 4096:.3f} us per frame)")
+        return
+    if a.stage == "harmonic":
+        print(f"harmonic: {us:.1f} us per call of 4096 frames = {4096 / us * 1e6:.0f} frames/s ({us / 4096:.3f} us per frame)")
         return
     print(f"{a.stage}: {us:.1f} us per call, {us * 1e3 / ncf:.1f} ns per channel-frame ({ncf} cf)" +
           (f" = {ncf / us * 1e6:.0f} channel-frames/s (host in/out)" if a.stage == "host" else ""))
