@@ -53,6 +53,7 @@ hipError_t launch_transients_any(const TransientParams& p, hipStream_t s);
 hipError_t launch_post(const PostParams& p, hipStream_t s);
 hipError_t launch_pitch(const PitchParams& p, hipStream_t s);
 hipError_t launch_harmonic(const HarmonicParams& p, hipStream_t s);
+hipError_t launch_genre(const GenreParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -377,6 +378,13 @@ struct omega_ctx {
   float* d_hprev[2] = {};
   int harm_cur = 0;
   std::map<int, double*> harm_ham;
+  // genre features (omega_genre_configure / omega_genre_features): the configuration with the band ranges,
+  // the frequency table and the previous frame's magnitude (double-buffered, a state of its own)
+  bool genre_set = false, genre_has_prev = false;
+  GenreParams genre{};
+  double* d_gfreqs = nullptr;
+  float* d_gprev[2] = {};
+  int genre_cur = 0;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables
@@ -2121,6 +2129,153 @@ int omega_harmonic_metrics(omega_ctx* c, const float* spectrum, const float* pre
   p.prev_out = nullptr;
   p.out = dout;
   HIPC(c, launch_harmonic(p, c->stream));
+  if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+void omega_genre_config_default(omega_genre_config* cfg) {
+  if (!cfg) return;
+  *cfg = omega_genre_config{};
+  cfg->sample_rate = 48000;
+  cfg->n_bins = 512;
+}
+
+int omega_genre_configure(omega_ctx* c, const omega_genre_config* cfg, const double* freqs) try {
+  if (!c || !cfg) return OMEGA_EINVAL;
+  if (!freqs) return fail(c, OMEGA_EINVAL, "genre: freqs is NULL");
+  if (cfg->sample_rate <= 0) return fail(c, OMEGA_EINVAL, "genre: need sample_rate > 0");
+  if (cfg->n_bins < 2) return fail(c, OMEGA_EINVAL, "genre: n_bins %d", cfg->n_bins);
+  if (cfg->n_bins < kHarmonicMinBins || cfg->n_bins > kHarmonicMaxBins)
+    return fail(c, OMEGA_EUNSUP, "genre: %d spectrum bins (%d..%d are built)", cfg->n_bins, kHarmonicMinBins,
+                kHarmonicMaxBins);
+  const int K = cfg->n_bins;
+  for (int i = 0; i < K; ++i)
+    if (!std::isfinite(freqs[i]) || (i && !(freqs[i] > freqs[i - 1])))
+      return fail(c, OMEGA_EINVAL, "genre: freqs must be finite and strictly increasing (entry %d)", i);
+  HIPC(c, hipSetDevice(c->device));
+  if (c->d_gfreqs) {  // a reconfiguration: work already enqueued may still read the old tables
+    HIPC(c, hipStreamSynchronize(c->stream));
+    for (void* q : {(void*)c->d_gfreqs, (void*)c->d_gprev[0], (void*)c->d_gprev[1]}) {
+      auto it = std::find(c->allocs.begin(), c->allocs.end(), q);
+      if (it != c->allocs.end()) c->allocs.erase(it);
+      if (q) (void)hipFree(q);
+    }
+    c->d_gfreqs = nullptr;
+    c->d_gprev[0] = c->d_gprev[1] = nullptr;
+    c->genre_set = false;
+  }
+  const std::vector<double> tab(freqs, freqs + K);
+  int e = upload(c, &c->d_gfreqs, tab);
+  for (int b = 0; b < 2 && !e; ++b) e = dalloc(c, &c->d_gprev[b], (size_t)K);
+  if (e) return e;
+  GenreParams p{};
+  p.n_bins = K;
+  p.freqs = c->d_gfreqs;
+  // the reference's masks, with its own comparisons in float64; over an increasing table each is one range
+  auto in_band = [](int b, double f) {
+    switch (b) {
+      case 0: return f >= 20 && f <= 250;      // compute_bass_emphasis: bass
+      case 1: return f > 250 && f <= 2000;     //                        mid
+      case 2: return f >= 200 && f <= 4000;    // compute_vocal_presence: vocal
+      case 3: return f >= 300 && f <= 3000;    //                         core
+      case 4: return f >= 4000 && f <= 10000;  // compute_high_freq_energy: high
+      case 5: return f <= 10000;               //                           total
+      case 6: return f >= 20 && f < 500;       // compute_mid_frequency_dominance: low
+      case 7: return f >= 500 && f <= 2000;    //                                  mid
+      case 8: return f > 2000 && f <= 8000;    //                                  high
+      default: return f >= 100 && f <= 4000;   // compute_spectral_complexity
+    }
+  };
+  for (int b = 0; b < kGenreBands; ++b) {
+    int lo = 0, n = 0;
+    for (int i = 0; i < K; ++i)
+      if (in_band(b, freqs[i])) {
+        if (!n) lo = i;
+        ++n;
+      }
+    p.band_lo[b] = lo;
+    p.band_n[b] = n;
+  }
+  c->genre = p;
+  c->genre_cur = 0;
+  c->genre_has_prev = false;
+  c->genre_set = true;
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_genre_reset(omega_ctx* c) try {
+  if (!c) return OMEGA_EINVAL;
+  c->genre_has_prev = false;
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_genre_features(omega_ctx* c, const float* spectra, int64_t spec_stride, const void* audio, int32_t f64,
+                         int32_t m, int64_t audio_stride, int64_t n_frames, double* out, int32_t* peak_bins,
+                         int mem) try {
+  if (!c || !out || !peak_bins) return OMEGA_EINVAL;
+  if (!c->genre_set) return fail(c, OMEGA_EINVAL, "genre: omega_genre_configure has not been called");
+  const int K = c->genre.n_bins;
+  if (!spectra || n_frames < 0 || spec_stride < 1) return fail(c, OMEGA_EINVAL, "genre: bad spectrum layout");
+  if (!audio || m <= 0 || audio_stride < 1) return fail(c, OMEGA_EINVAL, "genre: bad audio layout");
+  if (m < kHarmonicMinAudio || m > kHarmonicMaxAudio)
+    return fail(c, OMEGA_EUNSUP, "genre: %d audio samples per frame (%d..%d are built)", m, kHarmonicMinAudio,
+                kHarmonicMaxAudio);
+  if (n_frames == 0) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  std::vector<HostOut> outs;
+  const float* dspec = spectra;
+  const void* daudio = audio;
+  double* dout = out;
+  int32_t* dbins = peak_bins;
+  if (mem == OMEGA_MEM_HOST) {
+    const void* q = nullptr;
+    int e = stage_in(c, 0, spectra, (size_t)((n_frames - 1) * spec_stride + K) * sizeof(float), &q);
+    dspec = static_cast<const float*>(q);
+    if (!e) e = stage_in(c, 1, audio, (size_t)((n_frames - 1) * audio_stride + m) * (f64 ? 8 : 4), &daudio);
+    if (!e) e = stage_out(c, 2, out, (size_t)n_frames * kGenreCols, outs, &dout);
+    if (!e) e = stage_out(c, 3, peak_bins, (size_t)n_frames * kGenrePeaks, outs, &dbins);
+    if (e) return e;
+  }
+  GenreParams p = c->genre;
+  p.spec_stride = spec_stride;
+  p.f64 = f64 ? 1 : 0;
+  p.m = m;
+  p.audio_stride = audio_stride;
+  // np.percentile's virtual index (m - 1) q with q = 95 / 100 and 20 / 100 in the audio's precision
+  if (f64) {
+    const double v95 = (double)(m - 1) * (95.0 / 100.0), v20 = (double)(m - 1) * (20.0 / 100.0);
+    p.rank95 = (int)std::floor(v95), p.gamma95 = v95 - std::floor(v95);
+    p.rank20 = (int)std::floor(v20), p.gamma20 = v20 - std::floor(v20);
+  } else {
+    const volatile float q95 = 95.0f / 100.0f, q20 = 20.0f / 100.0f;
+    const volatile float v95 = (float)(m - 1) * q95, v20 = (float)(m - 1) * q20;
+    p.rank95 = (int)std::floor(v95), p.gamma95 = (double)v95 - std::floor((double)v95);
+    p.rank20 = (int)std::floor(v20), p.gamma20 = (double)v20 - std::floor((double)v20);
+  }
+  if (p.rank95 + 1 >= m || p.rank20 + 1 >= m) return fail(c, OMEGA_EINVAL, "genre: percentile rank outside the frame");
+  const int a = c->genre_cur, b = a ^ 1;
+  // one launch covers at most 2^30 workgroups (two per frame)
+  const int64_t per = (int64_t)1 << 29;
+  const size_t el = f64 ? 8 : 4;
+  for (int64_t f0 = 0; f0 < n_frames; f0 += per) {
+    GenreParams q = p;
+    q.n_frames = std::min(per, n_frames - f0);
+    q.spec = dspec + f0 * spec_stride;
+    q.audio = static_cast<const char*>(daudio) + (size_t)(f0 * audio_stride) * el;
+    q.prev_in = f0 ? dspec + (f0 - 1) * spec_stride : (c->genre_has_prev ? c->d_gprev[a] : nullptr);
+    q.prev_out = f0 + q.n_frames == n_frames ? c->d_gprev[b] : nullptr;
+    q.out = dout + f0 * kGenreCols;
+    q.peak_bins = dbins + f0 * kGenrePeaks;
+    HIPC(c, launch_genre(q, c->stream));
+  }
+  c->genre_cur = b;
+  c->genre_has_prev = true;
   if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
   return 0;
 } catch (...) {

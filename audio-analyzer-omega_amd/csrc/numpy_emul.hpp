@@ -84,6 +84,46 @@ __device__ __forceinline__ float np_leaf_combine(int n, const float* ls, int& id
     return a + b;
   }
 }
+// The slice form, np.sum(g(a[lo : lo + n])) for an elementwise float32 g: numpy copies the masked slice,
+// so its recursion sees a contiguous array of n elements whatever lo is. np_emit_leaves lists the
+// recursion's leaves (depth-first) as off | len << 16 with off counted from `off`; np_slice_leaf sums one
+// leaf of term(i), i = 0 .. n - 1, in numpy's order (any lane, any leaf); np_leaf_combine<D>(n, ...) adds
+// the leaf sums. D = 7 covers n <= 16384.
+template <int D>
+__device__ __forceinline__ void np_emit_leaves(int off, int n, unsigned* tab, int& idx) {
+  if constexpr (D == 0) {
+    tab[idx++] = (unsigned)off | ((unsigned)n << 16);
+  } else {
+    if (n <= 128) {
+      tab[idx++] = (unsigned)off | ((unsigned)n << 16);
+      return;
+    }
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    np_emit_leaves<D - 1>(off, n2, tab, idx);
+    np_emit_leaves<D - 1>(off + n2, n - n2, tab, idx);
+  }
+}
+template <class Term>
+__device__ __forceinline__ float np_slice_leaf(int n, Term term) {
+  if (n < 8) {
+    float r = 0.f;
+    for (int i = 0; i < n; ++i) r += term(i);
+    return r;
+  }
+  float r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = term(j);
+  int i = 8;
+  for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] += term(i + j);
+  }
+  float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += term(i);
+  return res;
+}
+
 // One wave's share of np_pairwise_sum(a, n): the leaf sums, one per leaf of the table, into
 // ls[0 .. tab[0]) -- 8 lanes per leaf, 8 leaves per pass. The caller publishes ls (a barrier) and
 // combines it with np_leaf_combine on one lane.

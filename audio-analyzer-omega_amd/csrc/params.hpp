@@ -503,6 +503,36 @@ struct HarmonicParams {
   double* series_strength;  // [n_frames, max_series] or nullptr
 };
 
+// GenreClassifier.extract_features (genre.hip; omega4/panels/genre_classification.py:175-422, :600-783):
+// two workgroup roles per frame (spectrum side, audio side) and a per-frame combine
+constexpr int kGenreCols = 17;  // centroid, rolloff, rolloff index, zero crossings, bandwidth, dynamic range, loud,
+                                // quiet, rms, spectral complexity, bass emphasis, vocal presence, high-frequency
+                                // energy, flux, distortion count, mid-frequency dominance, flags
+constexpr int kGenreThreads = 256;
+constexpr int kGenrePeaks = 5;   // compute_harmonic_distortion weighs the five largest peaks
+// the contiguous bin ranges of the reference's masks over the increasing table: bass [20, 250], its mid
+// (250, 2000], vocal [200, 4000], core vocal [300, 3000], high [4000, 10000], <= 10000, low [20, 500),
+// mid [500, 2000], upper (2000, 8000], and the flatness range [100, 4000]
+constexpr int kGenreBands = 10;
+struct GenreParams {
+  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values (|.| is taken)
+  int64_t spec_stride;
+  int n_bins;
+  const double* freqs;      // [n_bins] strictly increasing
+  const void* audio;        // frame f at audio + f * audio_stride (float32, or float64 when f64)
+  int f64;
+  int m;                    // audio samples per frame
+  int64_t audio_stride;
+  int64_t n_frames;
+  int band_lo[kGenreBands], band_n[kGenreBands];  // first bin and bin count of each range (0: no bins)
+  int rank95, rank20;       // floor(q (m - 1)) for np.percentile's q = 0.95 and 0.20, in the audio's precision
+  double gamma95, gamma20;  // q (m - 1) - rank
+  const float* prev_in;     // the magnitude frame 0's flux compares with, or nullptr (flux 0)
+  float* prev_out;          // [n_bins] the last frame's magnitude, or nullptr (not this launch's last)
+  double* out;              // [n_frames, kGenreCols]
+  int* peak_bins;           // [n_frames, kGenrePeaks] the largest peaks' bins, -1 past their number
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

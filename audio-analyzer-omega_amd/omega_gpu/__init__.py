@@ -8,9 +8,10 @@ from ._lib import LIB_PATH, OmegaError, UnsupportedError, lib
 from .engine import DEFAULT_RESOLUTIONS, METER_KEYS, NORTHSTAR_RESOLUTIONS, BandTable, Engine, Resolution
 from .pitch_detection import CepstralAnalyzer, PitchDetectionConfig, get_preset_config, list_presets
 from .harmonic_analysis import HarmonicAnalyzer, HarmonicMetrics
+from .genre_classification import GenreClassifier
 
 __all__ = [
-    "HarmonicAnalyzer", "HarmonicMetrics",
+    "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier",
     "LIB_PATH", "OmegaError", "UnsupportedError", "lib", "Engine", "Resolution", "BandTable",
     "DEFAULT_RESOLUTIONS", "NORTHSTAR_RESOLUTIONS", "METER_KEYS",
     "CepstralAnalyzer", "PitchDetectionConfig", "get_preset_config", "list_presets",

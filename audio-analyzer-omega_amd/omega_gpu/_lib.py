@@ -59,6 +59,10 @@ class HarmonicConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("n_bins", C.c_int32), ("max_series", C.c_int32)]
 
 
+class GenreConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("n_bins", C.c_int32)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -102,6 +106,11 @@ EXPORTS = {
     "omega_harmonic_reset": (C.c_int, [C.c_void_p]),
     "omega_harmonic_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                          C.c_double, C.c_void_p, C.c_int]),
+    "omega_genre_config_default": (None, [C.POINTER(GenreConfig)]),
+    "omega_genre_configure": (C.c_int, [C.c_void_p, C.POINTER(GenreConfig), C.c_void_p]),
+    "omega_genre_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
+    "omega_genre_reset": (C.c_int, [C.c_void_p]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -39,6 +39,8 @@
  *   omega_harmonic_*       HarmonicAnalyzer.detect_harmonic_series     omega4/panels/harmonic_analysis.py:193-333 with
  *                          HarmonicMetrics (THD, THD+N, spectral shape, HNR, LPC formants)
  *                          omega4/analyzers/harmonic_metrics.py:51-357 (§8(f) row 6)
+ *   omega_genre_*          GenreClassifier.extract_features            omega4/panels/genre_classification.py:175-422,
+ *                          :600-783 (§8(f) row 7)
  *
  * Conventions:
  *   - every function returns 0 on success and a negative omega_status on error; the message is
@@ -436,6 +438,52 @@ int omega_harmonic_reset(omega_ctx* ctx);
  * written. */
 int omega_harmonic_metrics(omega_ctx* ctx, const float* spectrum, const float* previous, const void* audio,
                            int32_t f64, int32_t m, double fundamental, double* out, int mem);
+
+/* GenreClassifier.extract_features (omega4/panels/genre_classification.py:175-254 with the compute_* /
+ * estimate_* helpers, :256-422 and :600-783) for n_frames frames of one stream: the float32 spectrum of
+ * n_bins values at spectra + f*spec_stride (its magnitude is taken) over the float64 frequency table given
+ * to omega_genre_configure, and the frame's m audio samples (float32, or float64 when f64 != 0) at
+ * audio + f*audio_stride; rows may overlap. The entry points are additive to ABI 5: a caller detects them
+ * by their presence.
+ * out [n_frames, OMEGA_GENRE_COLS] float64, in this order:
+ *    0 spectral_centroid        float64 sum / np.sum(magnitude) (float32 pairwise); 0 for a zero sum
+ *    1 spectral_rolloff         freqs[min(index, n_bins - 1)]; 0 for a zero sum
+ *    2 rolloff_index            first index of the SEQUENTIAL float32 np.cumsum >= float32(0.85) cumsum[-1]
+ *    3 zero_crossings           count of nonzero np.diff(np.sign(x)) (the rate is this / m)
+ *    4 spectral_bandwidth
+ *    5 dynamic_range            min(1, (loud - quiet) / loud) if quiet > 0 else 0
+ *    6 loud, 7 quiet            np.percentile(|x|, 95) and (|x|, 20), in the audio's precision
+ *    8 rms                      np.sqrt(np.mean(x ** 2)) (the panel's silence gate; the device does not gate)
+ *    9 spectral_complexity      1 - flatness over 100..4000 Hz, evaluated in float64; 0.3 where the reference says so
+ *   10 bass_emphasis, 11 vocal_presence, 12 high_freq_energy   float32, operation for operation
+ *   13 spectral_flux            against the previous frame's magnitude; 0 for the first frame after
+ *                               configure / reset
+ *   14 distortion_count         qualifying peaks among the five largest (harmonic_distortion = min(0.2 x, 1))
+ *   15 mid_frequency_dominance
+ *   16 flags                    bit 1: non-finite input. A frame with a non-finite sample or bin gives the
+ *                               zero row; its magnitude is stored like any other, the next frame's flux
+ *                               leaves the non-finite bins out and carries the flag
+ * peak_bins [n_frames, OMEGA_GENRE_PEAKS] int32: the bins of the five largest strict local maxima above
+ * float32(np.mean(magnitude) * 2), largest first, ties to the lower bin, -1 past their number.
+ * Flux state: frame f compares with frame f-1 of the call, frame 0 with the magnitude the context kept
+ * from the previous call; omega_genre_reset forgets it, omega_genre_configure (which must precede
+ * omega_genre_features and may be repeated with another table) does too. It is a state of its own, apart
+ * from omega_harmonic_analyze's.
+ * Supported: 16 <= n_bins <= 8193, strictly increasing freqs, 15 <= m <= 8192; other sizes return
+ * OMEGA_EUNSUP. The drum, harmonic-series, chroma and history features and classify() are scalar host work
+ * left to the caller. */
+#define OMEGA_GENRE_COLS 17
+#define OMEGA_GENRE_PEAKS 5
+typedef struct {
+  int32_t sample_rate;
+  int32_t n_bins;                    /* entries of freqs and bins per spectrum */
+} omega_genre_config;
+/* 48000 Hz, 512 bins (the app's combined spectrum). */
+void omega_genre_config_default(omega_genre_config* cfg);
+int omega_genre_configure(omega_ctx* ctx, const omega_genre_config* cfg, const double* freqs);
+int omega_genre_features(omega_ctx* ctx, const float* spectra, int64_t spec_stride, const void* audio, int32_t f64,
+                         int32_t m, int64_t audio_stride, int64_t n_frames, double* out, int32_t* peak_bins, int mem);
+int omega_genre_reset(omega_ctx* ctx);
 
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Run one stage of the cfg2 hot path in isolation (for rocprofv3 counter passes and A/B timing).
 
-  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic} [--reps N]
+  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre} [--reps N]
 
 spectra-bands / spectra-chroma / spectra-mag: the cfg3 kernel with one output set only (where its LDS
 bank conflicts and time come from); spectra-rot: bench.py's cfg3 call, rotating over 4 distinct input
@@ -25,6 +25,7 @@ def main():
     ap.add_argument("stage")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--frames", type=int, default=256, help="stereo frames per call (cfg2: 256, cfg4 shard: 4096)")
+    ap.add_argument("--bins", type=int, default=512, help="genre: spectrum bins per frame (512, 4097)")
     ap.add_argument("--lib", default=None, help="another build in lib/ (A/B of two builds on one box)")
     a = ap.parse_args()
     if a.lib:
@@ -98,6 +99,24 @@ def main():
         hss = torch.empty(4096, 16, dtype=torch.float64, device="cuda")
         han._eng._bind_stream(hs)
 
+    if a.stage == "genre":  # GenreClassifier features over 4096 resident frames: 512-bin spectra, 2048-sample audio
+        from omega_gpu.genre_classification import COLUMNS as GCOLS, GenreClassifier
+        rng = np.random.default_rng(9)
+        gfr = np.linspace(0, 24000, a.bins)
+        tt = np.arange(2048) / 48000.0
+        f0 = np.linspace(0, 24000, 512)[rng.integers(3, 40, 4096)][:, None]
+        gx = sum((1.0 / (k + 1)) * np.sin(2 * np.pi * f0 * (k + 1) * tt[None, :]) for k in range(8))
+        gx = ((0.3 * gx + 0.002 * rng.standard_normal(gx.shape)) * np.hanning(2048)).astype(np.float32)
+        nfft = 2 * (a.bins - 1)
+        gs = np.abs(np.fft.rfft(np.resize(gx, (4096, nfft)) * np.hanning(nfft), axis=1))
+        gs = torch.from_numpy((gs / gs.max(axis=1, keepdims=True)).astype(np.float32)).cuda()
+        gx = torch.from_numpy(gx).cuda()
+        gen = GenreClassifier(48000)
+        gen.extract_features_frames(gs[:1], gfr, gx[:1])  # (configures the table)
+        gout = torch.empty(4096, len(GCOLS), dtype=torch.float64, device="cuda")
+        gpb = torch.empty(4096, 5, dtype=torch.int32, device="cuda")
+        gen._eng._bind_stream(gs)
+
     outs = L.Outputs()
     outs.combined, outs.lufs_inst, outs.true_peak_db = comb.data_ptr(), out["li"].data_ptr(), out["tp"].data_ptr()
 
@@ -139,6 +158,9 @@ def main():
         if a.stage == "harmonic":
             han._eng._check(lib.omega_harmonic_analyze(han._eng._ctx, hs.data_ptr(), 512, hx.data_ptr(), 1, 2048, 2048,
                                                        4096, hout.data_ptr(), hsb.data_ptr(), hss.data_ptr(), L.MEM_DEVICE))
+        if a.stage == "genre":
+            gen._eng._check(lib.omega_genre_features(gen._eng._ctx, gs.data_ptr(), a.bins, gx.data_ptr(), 0, 2048, 2048,
+                                                     4096, gout.data_ptr(), gpb.data_ptr(), L.MEM_DEVICE))
         if a.stage == "host":  # host buffers in and out: PCIe-inclusive rate of the full path
             host_out.update(eng.process_frames(xh, 256, 2 * 16384, 16384, meters=True))
         if a.stage in ("tp", "all"):
@@ -169,6 +191,9 @@ def main():
         return
     if a.stage == "harmonic":
         print(f"harmonic: {us:.1f} us per call of 4096 frames = {4096 / us * 1e6:.0f} frames/s ({us / 4096:.3f} us per frame)")
+        return
+    if a.stage == "genre":
+        print(f"genre ({a.bins} bins): {us:.1f} us per call of 4096 frames = {4096 / us * 1e6:.0f} frames/s ({us / 4096:.3f} us per frame)")
         return
     print(f"{a.stage}: {us:.1f} us per call, {us * 1e3 / ncf:.1f} ns per channel-frame ({ncf} cf)" +
           (f" = {ncf / us * 1e6:.0f} channel-frames/s (host in/out)" if a.stage == "host" else ""))
