@@ -275,7 +275,9 @@ struct omega_ctx {
   unsigned seg_par[2] = {0, 0};
   // meter pipelining (omega_set_meter_pipelining): the meter segment of the last default-layout batch
   // with meters, not yet launched -- the next such batch launch runs it first in its grid, any other
-  // use of the meter state (and omega_synchronize / omega_flush_meters) launches it on its own
+  // use of the meter state (and omega_synchronize / omega_flush_meters) launches it on its own.
+  // (Where batches overlap -- bs below -- each call launches its own segment behind its batch on the
+  // batch's stream and nothing stays pending: `unjoined` takes the place of `pend`.)
   bool pipe = false;
   bool pend = false;
   MeterPrepParams pend_mq{};
@@ -292,6 +294,19 @@ struct omega_ctx {
   unsigned long long* d_mirror = nullptr;
   unsigned mirror_gen = 0;
   int tail_ok = 0;
+  // overlapped pipelined batches (omega_set_meter_pipelining, with tail_ok > 0): call i's batch launch
+  // and, behind it, its meter segment as a launch of its own go to bs[i & 1] (two non-blocking streams,
+  // created when pipelining is first enabled), batch i gated on batch i - 1's tail count; ev_done[k]
+  // follows the segment on bs[k], and the caller's stream waits for call i's only in call i + 1 (or a
+  // flush): `unjoined` = the call on bs[last_bs] is not yet ordered into the caller's stream.
+  // prev_span: what that call reads ([0]) and writes (the rest) -- a call touching any of it runs serial
+  hipStream_t bs[2] = {nullptr, nullptr};
+  hipEvent_t ev_in = nullptr, ev_done[2] = {nullptr, nullptr};
+  unsigned bs_idx = 0;
+  int last_bs = 0;
+  bool unjoined = false;
+  bool bs_shared = false;  // the last probe left a batch stream on a shared hardware queue (calls serialise)
+  std::vector<std::pair<const char*, size_t>> prev_span;
   // device-side poll expiry flags (host-mapped: [0] meter prep, [1] join), checked by
   // check_device_err; the poll bound (OMEGA_POLL_LIMIT, a test knob)
   unsigned* h_err = nullptr;
@@ -488,6 +503,8 @@ int grow(omega_ctx* c, T** p, int64_t* cap, int64_t need) {
     HIPC(c, hipStreamSynchronize(c->stream));
     for (hipStream_t f : c->fork)
       if (f) HIPC(c, hipStreamSynchronize(f));
+    for (hipStream_t f : c->bs)  // (an overlapped pipelined batch may still run there)
+      if (f) HIPC(c, hipStreamSynchronize(f));
     auto it = std::find(c->allocs.begin(), c->allocs.end(), static_cast<void*>(*p));
     if (it != c->allocs.end()) c->allocs.erase(it);
     (void)hipFree(*p);
@@ -512,7 +529,12 @@ int stage_buf(omega_ctx* c, int i, size_t bytes, void** out) {
   if ((int)c->stage.size() <= i) c->stage.resize(i + 1);
   DevBuf& b = c->stage[i];
   if (b.n < bytes) {
-    if (b.p) (void)hipFree(b.p);
+    if (b.p) {
+      // (an overlapped pipelined batch on a batch stream, or its meter segment, may still use the slot)
+      for (hipStream_t f : c->bs)
+        if (f) HIPC(c, hipStreamSynchronize(f));
+      (void)hipFree(b.p);
+    }
     b.p = nullptr;
     b.n = 0;
     const hipError_t e = hipMalloc(&b.p, std::max<size_t>(bytes, 256));
@@ -1108,11 +1130,23 @@ int meters_enqueue(omega_ctx* c, const float* lufs, const float* tp, int64_t n_f
   return 0;
 }
 
+// Overlapped pipelined batches: order the last call's batch stream (batch, then meter segment) into the
+// context's stream. (The call before it was joined when the last one was enqueued.)
+int join_batches(omega_ctx* c) {
+  if (!c->unjoined) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamWaitEvent(c->stream, c->ev_done[c->last_bs], 0));
+  c->unjoined = false;
+  c->prev_span.clear();
+  return 0;
+}
+
 // Meter pipelining: the pending meter segment as a launch of its own on the context's stream (the
-// stream of the batch it belongs to: omega_set_stream flushes before switching).
-// Meter pipelining: the pending meter segment as a launch of its own on the context's stream (the
-// stream of the batch it belongs to: omega_set_stream flushes before switching).
-int flush_meters(omega_ctx* c) {
+// stream of the batch it belongs to: omega_set_stream flushes before switching), or on `on` (an
+// overlapped call's batch stream); an overlapped call still on its batch stream is joined first.
+int flush_meters(omega_ctx* c, hipStream_t on = nullptr) {
+  if (!on)
+    if (int e = join_batches(c)) return e;
   if (!c->pend) return 0;
   HIPC(c, hipSetDevice(c->device));
   BatchPlan bp{};
@@ -1121,11 +1155,26 @@ int flush_meters(omega_ctx* c) {
   bp.seg_start[0] = bp.seg_start[1] = bp.multi_start = c->pend_nq;  // (no other workgroups)
   SpectralParams sp{};
   KWeightParams kp{};
-  const hipError_t le = launch_batch(sp, kp, bp, c->pend_mq, c->pend_nq, c->stream);
+  const hipError_t le = launch_batch(sp, kp, bp, c->pend_mq, c->pend_nq, on ? on : c->stream);
   if (le != hipSuccess) return fail(c, OMEGA_EHIP, "meter segment launch: %s", hipGetErrorString(le));
   c->pend = false;
   c->seg_par[c->pend_par] = c->seg_issued + (unsigned)c->pend_nq;
   c->seg_issued += (unsigned)c->pend_nq;
+  return 0;
+}
+
+// The signal-memory word of omega_ctx::d_tail, on first use (tail_ok: 1 ready, -1 no stream-wait-value
+// support on this device).
+int tail_init(omega_ctx* c) {
+  if (c->tail_ok != 0) return 0;
+  int ok = 0;
+  HIPC(c, hipDeviceGetAttribute(&ok, hipDeviceAttributeCanUseStreamWaitValue, c->device));
+  c->tail_ok = -1;
+  if (ok && hipExtMallocWithFlags(reinterpret_cast<void**>(&c->d_tail), 8, hipMallocSignalMemory) == hipSuccess) {
+    HIPC(c, hipMemset(c->d_tail, 0, 8));
+    c->tail_issued = 0;
+    c->tail_ok = 1;
+  }
   return 0;
 }
 
@@ -1284,16 +1333,8 @@ int enqueue_batch(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int6
       p.wait_ctr = c->d_kw_done;
       p.wait_target = c->kw_issued;
     }
-    if (fold && c->tail_ok == 0) {
-      int ok = 0;
-      HIPC(c, hipDeviceGetAttribute(&ok, hipDeviceAttributeCanUseStreamWaitValue, c->device));
-      c->tail_ok = -1;
-      if (ok && hipExtMallocWithFlags(reinterpret_cast<void**>(&c->d_tail), 8, hipMallocSignalMemory) == hipSuccess) {
-        HIPC(c, hipMemset(c->d_tail, 0, 8));
-        c->tail_issued = 0;
-        c->tail_ok = 1;
-      }
-    }
+    if (fold)
+      if (int e = tail_init(c)) return e;
     const bool tail = fold && c->tail_ok > 0;
     if (tail) bp.tail_ctr = c->d_tail;
     // unpipelined: the prep before the batch (it must be resident while the batch runs: its segment
@@ -1405,6 +1446,73 @@ hipError_t create_side_stream(hipStream_t* st) { return hipStreamCreateWithFlags
 // since, e.g. an RCCL communicator's, may have been dealt onto the side stream's queue).
 constexpr int kProbePolls = 2048;  // x ~0.3 us: the waiter's bound (paid only on a shared queue)
 constexpr size_t kMaxSpare = 6;
+// `*st` shares a hardware queue it should not: keep it as a spare (so the next stream created lands on
+// another queue) and take a new one. The replacement is created BEFORE the oldest spare beyond
+// kMaxSpare is destroyed: destroying first could free the very queue that was found shared and put
+// the new stream back on it.
+int replace_side_stream(omega_ctx* c, hipStream_t* st) {
+  hipStream_t fresh = nullptr;
+  HIPC(c, create_side_stream(&fresh));
+  c->spare.push_back(*st);
+  *st = fresh;
+  if (c->spare.size() > kMaxSpare) {
+    HIPC(c, hipStreamDestroy(c->spare.front()));
+    c->spare.erase(c->spare.begin());
+  }
+  return 0;
+}
+
+// One probe of a pair of idle streams: *ind = a kernel on `setter` ran beside a waiting one on `waiter`.
+int probe_pair(omega_ctx* c, hipStream_t waiter, hipStream_t setter, bool* ind) {
+  const unsigned target = ++c->probe_seq;  // (w[0] holds the previous one: never equal)
+  HIPC(c, launch_queue_probe(c->d_probe, target, kProbePolls, waiter, setter));
+  HIPC(c, hipStreamSynchronize(waiter));
+  HIPC(c, hipStreamSynchronize(setter));
+  unsigned r[2] = {0u, 0u};
+  HIPC(c, hipMemcpy(r, c->d_probe, sizeof r, hipMemcpyDeviceToHost));
+  *ind = r[1] == target;
+  return 0;
+}
+
+// The batch streams of overlapped pipelined calls (omega_ctx::bs), probed like the side stream: each
+// against fork[0] (the meter prep polls beside the batch, and the batch's meter segment polls the prep's
+// count), against the context's stream (an entry event recorded behind a batch on a shared queue would
+// hold the next batch until this one ends) and against each other (the overlap itself). A batch stream
+// on a shared queue is replaced, three times at most; after that the calls serialise on that queue
+// (every stream wait follows the work it waits for) and the device waits stay bounded.
+int batch_stream_check(omega_ctx* c) {
+  c->bs_shared = false;
+  if (!c->bs[0]) return 0;
+  if (!c->d_probe) {
+    HIPC(c, hipMalloc(&c->d_probe, 2 * sizeof(unsigned)));
+    HIPC(c, hipMemset(c->d_probe, 0, 2 * sizeof(unsigned)));
+  }
+  HIPC(c, hipStreamSynchronize(c->stream));
+  HIPC(c, hipStreamSynchronize(c->fork[0]));
+  for (int k = 0; k < 2; ++k) {
+    HIPC(c, hipStreamSynchronize(c->bs[k]));
+    bool ind = false;
+    for (int attempt = 0;; ++attempt) {  // (the last replacement is probed too)
+      if (int e = probe_pair(c, c->fork[0], c->bs[k], &ind)) return e;
+      if (ind)
+        if (int e = probe_pair(c, c->bs[k], c->stream, &ind)) return e;
+      if (ind && k == 1)
+        if (int e = probe_pair(c, c->bs[0], c->bs[1], &ind)) return e;
+      if (ind || attempt == 3) break;
+      if (int e = replace_side_stream(c, &c->bs[k])) return e;
+    }
+    if (!ind) c->bs_shared = true;
+  }
+  // Not an error and not what omega_check_queues returns (that is the side stream's queue, on which the
+  // device waits depend): overlapped calls then serialise, and omega_last_error says so.
+  if (c->bs_shared && !c->queue_shared)
+    std::snprintf(c->err, sizeof c->err,
+                  "batch streams: no hardware queues independent of the context's stream, the side stream and "
+                  "each other found after 3 attempts (more streams than GPU_MAX_HW_QUEUES?): consecutive "
+                  "pipelined batch calls serialise instead of overlapping");
+  return 0;
+}
+
 int side_stream_check(omega_ctx* c, bool force = false) {
   if (!force && std::find(c->checked.begin(), c->checked.end(), c->stream) != c->checked.end()) return 0;
   if (!c->d_probe) {
@@ -1425,26 +1533,22 @@ int side_stream_check(omega_ctx* c, bool force = false) {
     if (r[1] == target) {
       c->queue_shared = false;
       c->checked.push_back(c->stream);
-      return 0;
+      return batch_stream_check(c);
     }
     // a new side stream: what was checked against the old one no longer holds
     c->checked.clear();
-    if (c->spare.size() >= kMaxSpare) {
-      HIPC(c, hipStreamDestroy(c->spare.front()));
-      c->spare.erase(c->spare.begin());
-    }
-    c->spare.push_back(c->fork[0]);
-    c->fork[0] = nullptr;
-    HIPC(c, create_side_stream(&c->fork[0]));
+    if (int e = replace_side_stream(c, &c->fork[0])) return e;
   }
   // No independent queue found: not an error (the device waits stay bounded, omega.h), but reported --
   // omega_check_queues returns it, and omega_last_error says why the batch path may return OMEGA_EHIP.
   // The stream is not marked checked: the next switch to it probes again.
   c->queue_shared = true;
+  if (int e = batch_stream_check(c)) return e;  // (the batch streams against this side stream all the same)
   std::snprintf(c->err, sizeof c->err,
                 "side stream: no hardware queue independent of the context's stream found after 3 attempts "
                 "(more streams than GPU_MAX_HW_QUEUES?): batch-path device waits may run to their bound "
-                "(OMEGA_POLL_LIMIT) and return OMEGA_EHIP");
+                "(OMEGA_POLL_LIMIT) and return OMEGA_EHIP%s",
+                c->bs_shared ? "; the batch streams share queues too: pipelined batch calls serialise" : "");
   return 0;
 }
 
@@ -1456,7 +1560,7 @@ int side_stream_check(omega_ctx* c, bool force = false) {
 // lufs_st / tp_st: the context's staging slots of a pipelined call with meters (omega_process_frames).
 int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int64_t n_frames, const float* lufs,
                    const float* tp, double* meters, hipStream_t s, bool pipe = false, float* lufs_st = nullptr,
-                   float* tp_st = nullptr) {
+                   float* tp_st = nullptr, bool serial = false) {
   const bool do_tp = sp.tp_out != nullptr, do_kw = kp.lufs_out || kp.weighted_out;
   const bool do_res = sp.comb_out != nullptr || sp.res[0].mag_out || sp.res[1].mag_out || sp.res[2].mag_out ||
                       sp.res[3].mag_out;
@@ -1465,7 +1569,11 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
   // a pending meter segment goes first: folded into this batch's launch when it has an in-grid meter
   // segment of its own, else on its own
   const bool fold = pipe && batch && meters && do_tp && do_kw && n_frames > 0 && n_frames <= kChunkFrames;
-  if (c->pend && !fold)
+  // overlapped (omega_ctx::bs): the batch and, behind it, its own meter segment on a batch stream
+  if (fold && c->bs[0])
+    if (int e = tail_init(c)) return e;
+  const bool ovl = fold && c->bs[0] && c->tail_ok > 0;
+  if ((c->pend && (!fold || ovl)) || (c->unjoined && !ovl))
     if (int e = flush_meters(c)) return e;
   if (fold && lufs_st && tp_st) {
     // the segment and the prep read the staging slots; the caller's buffers get copies
@@ -1475,6 +1583,49 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
     sp.tp_out = tp_st;
     lufs = lufs_st;
     tp = tp_st;
+  }
+  if (ovl) {
+    const int k = (int)(c->bs_idx & 1);
+    hipStream_t b = c->bs[k];
+    // serial: this call touches memory the unjoined call reads or writes -- that one first
+    if (serial)
+      if (int e = join_batches(c)) return e;
+    // the input dependency: what the caller enqueued so far, before anything of this call
+    HIPC(c, hipEventRecord(c->ev_in, s));
+    HIPC(c, hipStreamWaitEvent(b, c->ev_in, 0));
+    // the gate: batch i starts placing workgroups once batch i - 1 has none left to place (its
+    // last-dispatched workgroup has bumped the tail count) and fills the slots its drain frees. The
+    // wait follows the launch it waits for (the previous call's): shared hardware queues serialise
+    if (c->tail_issued)
+      HIPC(c, hipStreamWaitValue32(b, c->d_tail, c->tail_issued, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    const int err = [&]() -> int {
+      if (int e = enqueue_batch(c, sp, kp, W, n_frames, lufs, tp, meters, b, mr, do_tp, do_kw, true)) return e;
+      // this call's meter segment, a launch of its own behind its batch: it polls the prep's count (the
+      // prep is enqueued: fork[0], behind the tail wait) and runs beside the next call's batch. Segments
+      // run in call order (each reads the true-peak history the one before rolled)
+      if (c->unjoined) HIPC(c, hipStreamWaitEvent(b, c->ev_done[k ^ 1], 0));
+      if (int e = flush_meters(c, b)) return e;
+      HIPC(c, hipEventRecord(c->ev_done[k], b));
+      // the deferred join: the caller's stream waits for the PREVIOUS call here, for this one in the
+      // next call (or a flush), so the next call's input dependency does not hold this batch's drain
+      if (c->unjoined) HIPC(c, hipStreamWaitEvent(s, c->ev_done[k ^ 1], 0));
+      return 0;
+    }();
+    if (err) {
+      // a step failed, possibly with the batch already on its stream: order whatever runs on both batch
+      // streams into the caller's stream now (a segment left pending is then launched there, behind
+      // its batch, by the next flush) and leave nothing unjoined
+      (void)hipEventRecord(c->ev_done[k], b);
+      if (c->unjoined) (void)hipStreamWaitEvent(s, c->ev_done[k ^ 1], 0);
+      (void)hipStreamWaitEvent(s, c->ev_done[k], 0);
+      c->unjoined = false;
+      c->prev_span.clear();
+      return err;
+    }
+    c->unjoined = true;
+    c->last_bs = k;
+    ++c->bs_idx;
+    return 0;
   }
   if (batch) return enqueue_batch(c, sp, kp, W, n_frames, lufs, tp, meters, s, mr, do_tp, do_kw, fold);
   if (do_kw) HIPC(c, launch_kweight(W, kp, s));
@@ -2520,7 +2671,9 @@ int omega_post_process(omega_ctx* c, const float* spectra, int64_t n_frames, int
 void omega_destroy(omega_ctx* c) try {
   if (!c) return;
   if (c->device >= 0) (void)hipSetDevice(c->device);
-  if (c->pend && !flush_meters(c)) (void)hipStreamSynchronize(c->stream);  // (the last call's meters)
+  if ((c->pend || c->unjoined) && !flush_meters(c)) (void)hipStreamSynchronize(c->stream);  // (the last call's meters)
+  for (hipStream_t st : c->bs)
+    if (st) (void)hipStreamSynchronize(st);
   if (c->own) (void)hipStreamSynchronize(c->own);
   if (c->fork[0]) (void)hipStreamSynchronize(c->fork[0]);
   for (void* p : c->allocs) (void)hipFree(p);
@@ -2539,11 +2692,11 @@ void omega_destroy(omega_ctx* c) try {
   if (c->h_err) (void)hipHostFree(c->h_err);
   if (c->d_tail) (void)hipFree(c->d_tail);
   if (c->d_mirror) (void)hipFree(c->d_mirror);
-  for (hipStream_t st : {c->cap, c->fork[0]})
+  for (hipStream_t st : {c->cap, c->fork[0], c->bs[0], c->bs[1]})
     if (st) (void)hipStreamDestroy(st);
   for (hipStream_t st : c->spare) (void)hipStreamDestroy(st);
   if (c->d_probe) (void)hipFree(c->d_probe);
-  for (hipEvent_t ev : {c->ev_fork, c->ev_join[0], c->ev_join[1], c->ev_kw})
+  for (hipEvent_t ev : {c->ev_fork, c->ev_join[0], c->ev_join[1], c->ev_kw, c->ev_in, c->ev_done[0], c->ev_done[1]})
     if (ev) (void)hipEventDestroy(ev);
   if (c->own) (void)hipStreamDestroy(c->own);
   delete c;
@@ -2556,7 +2709,7 @@ int omega_set_stream(omega_ctx* c, void* s) try {
   if (!c) return OMEGA_EINVAL;
   const hipStream_t ns = static_cast<hipStream_t>(s);  // NULL = the null (default) stream, e.g. torch's
   if (ns != c->stream) {
-    if (c->pend) {  // (a pending meter segment runs on its batch's stream)
+    if (c->pend || c->unjoined) {  // (a pending meter segment runs on its batch's stream)
       HIPC(c, hipSetDevice(c->device));
       if (int e = flush_meters(c)) return e;
     }
@@ -2580,7 +2733,7 @@ int omega_set_stream(omega_ctx* c, void* s) try {
 int omega_check_queues(omega_ctx* c, int* shared) try {
   if (!c) return OMEGA_EINVAL;
   HIPC(c, hipSetDevice(c->device));
-  if (c->pend) {  // (the probe synchronises both streams; a pending segment launches first)
+  if (c->pend || c->unjoined) {  // (the probe synchronises the streams; a pending segment launches first)
     if (int e = flush_meters(c)) return e;
   }
   if (int e = side_stream_check(c, true)) return e;
@@ -2601,7 +2754,7 @@ int omega_get_config(const omega_ctx* c, omega_config* cfg, int* device) {
 
 int omega_set_graphs(omega_ctx* c, int enable) try {
   if (!c) return OMEGA_EINVAL;
-  if (c->pend) {
+  if (c->pend || c->unjoined) {
     HIPC(c, hipSetDevice(c->device));
     if (int e = flush_meters(c)) return e;
   }
@@ -2617,7 +2770,7 @@ int omega_set_graphs(omega_ctx* c, int enable) try {
 
 int omega_synchronize(omega_ctx* c) try {
   if (!c) return OMEGA_EINVAL;
-  if (c->pend) {
+  if (c->pend || c->unjoined) {
     HIPC(c, hipSetDevice(c->device));
     if (int e = flush_meters(c)) return e;
   }
@@ -2757,11 +2910,34 @@ int omega_process_frames(omega_ctx* c, const float* x, int64_t n_frames, int64_t
     if (meters) c->cur ^= (int)(((n_frames + kChunkFrames - 1) / kChunkFrames) & 1);
     return 0;
   }
-  e = enqueue_frames(c, sp, kp, W, n_frames, lufs, tp, meters, c->stream, pipe, lufs_st, tp_st);
+  // overlapped pipelined calls: what this call reads ([0]) and writes; one that touches what the call
+  // still on its batch stream writes, or writes what that one reads, waits for it (two overlapped
+  // launches never write the same bytes, and an output passed on as input is complete)
+  std::vector<std::pair<const char*, size_t>> span_now;
+  bool serial = false;
+  if (pipe) {
+    auto add = [&](const void* p, size_t bytes) {
+      if (p) span_now.emplace_back(static_cast<const char*>(p), bytes);
+    };
+    span_now.emplace_back(reinterpret_cast<const char*>(x), span * sizeof(float));
+    add(comb, (size_t)ncf * T * sizeof(float));
+    add(out->lufs_inst, (size_t)ncf * sizeof(float));
+    add(out->true_peak_db, (size_t)ncf * sizeof(float));
+    add(meters, (size_t)ncf * OMEGA_N_METERS * sizeof(double));
+    add(weighted, (size_t)ncf * W * sizeof(float));
+    for (int r = 0; r < c->cfg.n_res; ++r) add(mags[r], (size_t)ncf * (c->cfg.res[r].fft_size / 2 + 1) * sizeof(float));
+    if (c->unjoined)
+      for (size_t i = 0; i < span_now.size() && !serial; ++i)
+        for (size_t j = 0; j < c->prev_span.size() && !serial; ++j)
+          serial = (i || j) && span_now[i].first < c->prev_span[j].first + c->prev_span[j].second &&
+                   c->prev_span[j].first < span_now[i].first + span_now[i].second;
+  }
+  e = enqueue_frames(c, sp, kp, W, n_frames, lufs, tp, meters, c->stream, pipe, lufs_st, tp_st, serial);
   if (e) {
     if (pipe && meters) c->stage_par ^= 1;  // (a still-pending segment reads the slots of the other parity)
     return e;
   }
+  if (c->unjoined) c->prev_span.swap(span_now);
   if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
   return 0;
 } catch (...) {
@@ -2770,11 +2946,20 @@ int omega_process_frames(omega_ctx* c, const float* x, int64_t n_frames, int64_t
 
 int omega_set_meter_pipelining(omega_ctx* c, int enable) try {
   if (!c) return OMEGA_EINVAL;
-  if (!enable && c->pend) {
+  if (!enable && (c->pend || c->unjoined)) {
     HIPC(c, hipSetDevice(c->device));
     if (int e = flush_meters(c)) return e;
   }
   c->pipe = enable != 0;
+  if (c->pipe && !c->bs[0]) {
+    HIPC(c, hipSetDevice(c->device));
+    for (int k = 0; k < 2; ++k) {
+      HIPC(c, create_side_stream(&c->bs[k]));
+      HIPC(c, hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming));
+    }
+    HIPC(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
+    if (int e = batch_stream_check(c)) return e;
+  }
   return 0;
 } catch (...) {
   return guard_fail(c);
@@ -2782,7 +2967,7 @@ int omega_set_meter_pipelining(omega_ctx* c, int enable) try {
 
 int omega_flush_meters(omega_ctx* c) try {
   if (!c) return OMEGA_EINVAL;
-  if (!c->pend) return 0;
+  if (!c->pend && !c->unjoined) return 0;
   HIPC(c, hipSetDevice(c->device));
   return flush_meters(c);
 } catch (...) {

@@ -80,9 +80,10 @@ class Engine:
         self.W, self.C, self.T = cfg.frame_size, cfg.n_channels, cfg.target_bins
         self.device = device
         self._ingests = []  # weak references: stream ingests bound to this context, closed before it
-        # meter pipelining: the outputs of the last pipelined device call, held until its deferred meter
-        # segment is enqueued (the next call, a flush, synchronize, reset or close): the segment writes
-        # that call's meters, so their memory must not return to torch's caching allocator before then
+        # meter pipelining: the outputs and the input of the last pipelined device call, held until that
+        # call is ordered into the stream (the next call, a flush, synchronize, reset or close): its batch
+        # runs on a stream of the context's and reads the input / writes the outputs until then, so their
+        # memory must not return to torch's caching allocator before
         self._pipe = False
         self._held = None
         code = lib.omega_create(C.byref(cfg), int(device), C.byref(self._ctx))
@@ -140,15 +141,20 @@ class Engine:
         self._held = None  # (the reset enqueued a pending segment first)
 
     def set_meter_pipelining(self, enable: bool = True):
-        """omega_set_meter_pipelining: a batch call's meter aggregates are completed by the next batch
-        call's launch (or flush_meters / synchronize) instead of its own (omega.h)."""
+        """omega_set_meter_pipelining (omega.h). When on, a device-memory process_frames call with meters
+        runs on a stream of the context's, beside the call before it: EVERY tensor it returns, not only
+        ``meters``, is ordered into torch's current stream only by the next such call, flush_meters or
+        synchronize -- reading ``o['combined']`` straight after the call reads unfinished data -- and its
+        input must stay unmodified until then (the engine keeps both alive). Values are bitwise those of
+        the default."""
         self._check(L.lib().omega_set_meter_pipelining(self._ctx, int(bool(enable))))
         self._pipe = bool(enable)
         if not enable:
             self._held = None
 
     def flush_meters(self):
-        """Enqueue a pending meter segment on the context's stream (omega_flush_meters)."""
+        """omega_flush_meters: order the last pipelined call -- all its outputs, meters included -- into
+        the context's stream (a no-op without one)."""
         self._check(L.lib().omega_flush_meters(self._ctx))
         self._held = None
 
@@ -210,9 +216,10 @@ class Engine:
         else:
             self._check(L.lib().omega_process_frames(self._ctx, _ptr(x), int(n_frames), int(frame_stride),
                                                      int(channel_stride), C.byref(outs), mem))
-        # the previous pipelined call's segment is enqueued by now (this call, or the flush a non-pipelined
-        # call runs first); this call's may be pending: hold its outputs (see __init__)
-        self._held = o if (self._pipe and dev and meters) else None
+        # the previous pipelined call is ordered into the stream by now (this call, or the flush a
+        # non-pipelined call runs first); this call's batch may still run on the context's batch stream
+        # and its meters be pending: hold its outputs and its input (see __init__)
+        self._held = (o, x) if (self._pipe and dev and meters) else None
         return o
 
     def combine(self, mags: Dict[int, np.ndarray], n_cf: int = 1) -> np.ndarray:

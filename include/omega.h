@@ -149,7 +149,8 @@ const char* omega_version(void);
 int omega_set_stream(omega_ctx* ctx, void* hip_stream);
 /* Probe the context's stream and its side stream again, whatever was probed before (a stream switch
  * probes each distinct stream once): streams created since -- an RCCL communicator's, another library's
- * -- may share a hardware queue with the side stream. Moves the side stream as omega_set_stream does;
+ * -- may share a hardware queue with the side stream. Moves the side stream as omega_set_stream does
+ * (and, with meter pipelining enabled, re-probes the context's two batch streams the same way);
  * *shared (optional) = 1 if no independent queue was found (the device waits then run to their bound;
  * omega_last_error says so), else 0. Synchronises both streams (a pending meter segment launches
  * first). Not part of the reference surface: the multi-GPU host calls it once its collectives exist. */
@@ -186,7 +187,16 @@ int omega_synchronize(omega_ctx* ctx);
  * reused by the next call as soon as this call's stream work completes (they receive copies).
  * Outputs are bitwise those of the default. In this mode the batch kernel never waits for the side
  * stream (the meter prep follows it there behind a stream wait on the batch's last workgroup; only the
- * next launch's meter segment waits for the prep). */
+ * next launch's meter segment waits for the prep).
+ *
+ * Overlapped batches (devices with stream-wait-value support): with pipelining on, such a call's batch
+ * launch and, behind it, its meter segment run on one of two streams of the context's, in turn, so the
+ * drain of one call's launch runs under the start of the next. The call waits for what the caller's
+ * stream holds when it is made (its input may be produced there). ALL its outputs, not only its meters,
+ * are ordered into the caller's stream by the next batch call on the context, omega_flush_meters or
+ * omega_synchronize (and by every call listed above that launches a pending segment), and its INPUT
+ * must stay unmodified until then. A call whose input or outputs overlap the outputs of the call
+ * before it, or whose outputs overlap that call's input, waits for that call first. */
 int omega_set_meter_pipelining(omega_ctx* ctx, int enable);
 /* Enqueue a pending meter segment now (no-op without one); complete with the stream's work. */
 int omega_flush_meters(omega_ctx* ctx);
