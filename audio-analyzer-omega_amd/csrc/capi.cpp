@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -54,6 +55,7 @@ hipError_t launch_post(const PostParams& p, hipStream_t s);
 hipError_t launch_pitch(const PitchParams& p, hipStream_t s);
 hipError_t launch_harmonic(const HarmonicParams& p, hipStream_t s);
 hipError_t launch_genre(const GenreParams& p, hipStream_t s);
+hipError_t launch_hiphop(const HipHopParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -174,6 +176,56 @@ void butter4_highpass_sos(double fc, double fs, BiquadCoef out[2]) {
     c.a[2] = (1.0 - K * iq + K * K) / n;
   }
   for (double& b : out[0].b) b *= gain;
+}
+
+// scipy.signal.butter(4, [lo, hi], 'bandpass', fs=fs, output='sos') as scipy builds it: buttap's four
+// poles, lp2bp_zpk around wo = sqrt(w1 w2) with bw = w2 - w1 (w = 4 tan(pi f / fs): the prewarped edges
+// at scipy's internal rate 2), bilinear_zpk (four zeros at +1 from the origin, four at -1 from infinity),
+// then zpk2sos with pairing 'nearest': the pole pair nearest the unit circle is taken first and goes LAST,
+// each with the two remaining zeros nearest to it, the whole gain on the first section. Poles come in
+// exact conjugate pairs, so a = (1, -2 Re p, |p|^2). out[s] = b0 b1 b2 a0 a1 a2.
+void butter4_bandpass_sos(double lo, double hi, double fs, double out[4][6]) {
+  using cd = std::complex<double>;
+  const double w1 = 4.0 * std::tan(kPi * (2.0 * lo / fs) / 2.0), w2 = 4.0 * std::tan(kPi * (2.0 * hi / fs) / 2.0);
+  const double bw = w2 - w1, wo = std::sqrt(w1 * w2);
+  cd p[8];
+  for (int i = 0; i < 4; ++i) {
+    const int m = -3 + 2 * i;
+    const cd lp = -std::exp(cd(0.0, kPi * m / 8.0)) * bw / 2.0;
+    const cd r = std::sqrt(lp * lp - wo * wo);
+    p[i] = lp + r;
+    p[4 + i] = lp - r;
+  }
+  cd den(1.0, 0.0);
+  for (int i = 0; i < 8; ++i) den *= 4.0 - p[i];
+  const double gain = bw * bw * bw * bw * (cd(256.0, 0.0) / den).real();
+  std::vector<cd> pz;  // one pole of each conjugate pair
+  for (int i = 0; i < 8; ++i) {
+    const cd z = (4.0 + p[i]) / (4.0 - p[i]);
+    if (z.imag() > 0.0) pz.push_back(z);
+  }
+  int n_minus = 4, n_plus = 4;  // zeros left at -1 and at +1
+  for (int si = 0; si < 4 && !pz.empty(); ++si) {
+    size_t best = 0;
+    for (size_t i = 1; i < pz.size(); ++i)
+      if (std::abs(1.0 - std::abs(pz[i])) < std::abs(1.0 - std::abs(pz[best]))) best = i;
+    const cd p1 = pz[best];
+    pz.erase(pz.begin() + (long)best);
+    double z[2];
+    for (double& zz : z) {
+      const bool minus = n_minus > 0 && (n_plus == 0 || std::abs(p1 + 1.0) <= std::abs(p1 - 1.0));
+      zz = minus ? -1.0 : 1.0;
+      --(minus ? n_minus : n_plus);
+    }
+    double* o = out[3 - si];
+    o[0] = 1.0;
+    o[1] = -(z[0] + z[1]);
+    o[2] = z[0] * z[1];
+    o[3] = 1.0;
+    o[4] = -2.0 * p1.real();
+    o[5] = p1.real() * p1.real() + p1.imag() * p1.imag();
+  }
+  for (int k = 0; k < 3; ++k) out[0][k] *= gain;
 }
 
 void mat2_mul(const double* A, const double* B, double* C) {
@@ -400,6 +452,13 @@ struct omega_ctx {
   double* d_gfreqs = nullptr;
   float* d_gprev[2] = {};
   int genre_cur = 0;
+  // hip-hop features (omega_hiphop_configure / omega_hiphop_features): the configuration with the band
+  // ranges and the three band-pass cascades (no frame state), the designed sections as scipy lays them
+  // out, and per frame length the envelope transform's twiddle table
+  bool hiphop_set = false;
+  HipHopParams hiphop{};
+  double hiphop_sos[3][4][6] = {};
+  std::map<int, double2*> hiphop_tw;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables
@@ -2427,6 +2486,159 @@ int omega_genre_features(omega_ctx* c, const float* spectra, int64_t spec_stride
   }
   c->genre_cur = b;
   c->genre_has_prev = true;
+  if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+void omega_hiphop_config_default(omega_hiphop_config* cfg) {
+  if (!cfg) return;
+  *cfg = omega_hiphop_config{};
+  cfg->sample_rate = 48000;
+  cfg->n_bins = 512;
+}
+
+namespace {
+// the reference's filter bank (hip_hop_detector.py:70-92; bass_sos is never used): 0 sub-bass, 1 kick, 2 hi-hat
+void hiphop_design(int sample_rate, int which, double out[4][6]) {
+  const double nyquist = sample_rate / 2.0;
+  const double lo = which == 0 ? 20.0 : which == 1 ? 40.0 : 3000.0;
+  const double hi = which == 0 ? 60.0 : which == 1 ? 100.0 : std::min(10000.0, nyquist * 0.9);
+  butter4_bandpass_sos(lo, hi, (double)sample_rate, out);
+}
+}  // namespace
+
+int omega_hiphop_design_sos(int32_t sample_rate, int32_t which, double* out) try {
+  if (!out || which < 0 || which > 2 || sample_rate < kHipHopMinRate) return OMEGA_EINVAL;
+  double sos[4][6];
+  hiphop_design(sample_rate, which, sos);
+  std::memcpy(out, sos, sizeof sos);
+  return 0;
+} catch (...) {
+  return guard_fail(nullptr);
+}
+
+int omega_hiphop_configure(omega_ctx* c, const omega_hiphop_config* cfg, const double* freqs) try {
+  if (!c || !cfg) return OMEGA_EINVAL;
+  if (!freqs) return fail(c, OMEGA_EINVAL, "hiphop: freqs is NULL");
+  if (cfg->sample_rate <= 0) return fail(c, OMEGA_EINVAL, "hiphop: need sample_rate > 0");
+  if (cfg->sample_rate < kHipHopMinRate)
+    return fail(c, OMEGA_EUNSUP, "hiphop: sample rate %d (%d Hz and above are built)", cfg->sample_rate, kHipHopMinRate);
+  if (cfg->n_bins < 2) return fail(c, OMEGA_EINVAL, "hiphop: n_bins %d", cfg->n_bins);
+  if (cfg->n_bins < kHarmonicMinBins || cfg->n_bins > kHarmonicMaxBins)
+    return fail(c, OMEGA_EUNSUP, "hiphop: %d spectrum bins (%d..%d are built)", cfg->n_bins, kHarmonicMinBins,
+                kHarmonicMaxBins);
+  const int K = cfg->n_bins;
+  for (int i = 0; i < K; ++i)
+    if (!std::isfinite(freqs[i]) || (i && !(freqs[i] > freqs[i - 1])))
+      return fail(c, OMEGA_EINVAL, "hiphop: freqs must be finite and strictly increasing (entry %d)", i);
+  HipHopParams p{};
+  p.n_bins = K;
+  const double nyquist = cfg->sample_rate / 2.0;
+  // the reference's masks, with its own comparisons in float64; over an increasing table each is one range
+  auto in_band = [nyquist](int b, double f) {
+    switch (b) {
+      case 0: return f >= 20 && f <= 60;      // _detect_sub_bass: sub-bass
+      case 1: return f >= 60 && f <= 250;     //                   bass
+      case 2: return f < nyquist;             //                   total (the Nyquist bin is left out)
+      case 3: return f >= 20 && f <= 500;     // _analyze_spectral_tilt: low
+      case 4: return f >= 500 && f <= 2000;   //                         mid
+      case 5: return f >= 2000 && f <= 8000;  //                         high
+      case 6: return f >= 200 && f <= 3000;   // _detect_rap_vocals: vocal
+      case 7: return f >= 300 && f <= 2000;   //                     core
+      default: return true;                   //                     every bin
+    }
+  };
+  for (int b = 0; b < kHipHopBands; ++b) {
+    int lo = 0, n = 0;
+    for (int i = 0; i < K; ++i)
+      if (in_band(b, freqs[i])) {
+        if (!n) lo = i;
+        ++n;
+      }
+    p.band_lo[b] = lo;
+    p.band_n[b] = n;
+  }
+  for (int w = 0; w < 3; ++w) {
+    hiphop_design(cfg->sample_rate, w, c->hiphop_sos[w]);
+    for (int s = 0; s < 4; ++s) {
+      const double* q = c->hiphop_sos[w][s];
+      W64Stage& st = p.sos[w][s];
+      st.b0 = q[0], st.b1 = q[1], st.b2 = q[2], st.a1 = q[4], st.a2 = q[5];
+    }
+  }
+  p.distance = (int)(0.1 * cfg->sample_rate);
+  c->hiphop = p;
+  c->hiphop_set = true;
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_hiphop_get_sos(omega_ctx* c, int32_t which, double* out) try {
+  if (!c || !out) return OMEGA_EINVAL;
+  if (!c->hiphop_set) return fail(c, OMEGA_EINVAL, "hiphop: omega_hiphop_configure has not been called");
+  if (which < 0 || which > 2) return fail(c, OMEGA_EINVAL, "hiphop: filter %d (0 sub-bass, 1 kick, 2 hi-hat)", which);
+  std::memcpy(out, c->hiphop_sos[which], sizeof c->hiphop_sos[which]);
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_hiphop_features(omega_ctx* c, const float* spectra, int64_t spec_stride, const void* audio, int32_t f64,
+                          int32_t m, int64_t audio_stride, int64_t n_frames, double* out, int32_t* kick_peaks,
+                          int mem) try {
+  if (!c || !out) return OMEGA_EINVAL;
+  if (!c->hiphop_set) return fail(c, OMEGA_EINVAL, "hiphop: omega_hiphop_configure has not been called");
+  const int K = c->hiphop.n_bins;
+  if (!spectra || n_frames < 0 || spec_stride < 1) return fail(c, OMEGA_EINVAL, "hiphop: bad spectrum layout");
+  if (!audio || m <= 0 || audio_stride < 1) return fail(c, OMEGA_EINVAL, "hiphop: bad audio layout");
+  if (!is_pow2_in(m, kHipHopMinAudio, kHipHopMaxAudio))
+    return fail(c, OMEGA_EUNSUP, "hiphop: %d audio samples per frame (the powers of two %d..%d are built)", m,
+                kHipHopMinAudio, kHipHopMaxAudio);
+  if (n_frames == 0) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  auto it = c->hiphop_tw.find(m);
+  if (it == c->hiphop_tw.end()) {
+    std::vector<double2> tw((size_t)m / 2 + 1);
+    for (int q = 0; q <= m / 2; ++q) tw[q] = make_double2(std::cos(2 * M_PI * q / m), -std::sin(2 * M_PI * q / m));
+    double2* d = nullptr;
+    if (int e = upload(c, &d, tw)) return e;
+    it = c->hiphop_tw.emplace(m, d).first;
+  }
+  std::vector<HostOut> outs;
+  const float* dspec = spectra;
+  const void* daudio = audio;
+  double* dout = out;
+  int32_t* dpeaks = kick_peaks;
+  if (mem == OMEGA_MEM_HOST) {
+    const void* q = nullptr;
+    int e = stage_in(c, 0, spectra, (size_t)((n_frames - 1) * spec_stride + K) * sizeof(float), &q);
+    dspec = static_cast<const float*>(q);
+    if (!e) e = stage_in(c, 1, audio, (size_t)((n_frames - 1) * audio_stride + m) * (f64 ? 8 : 4), &daudio);
+    if (!e) e = stage_out(c, 2, out, (size_t)n_frames * kHipHopCols, outs, &dout);
+    if (!e) e = stage_out(c, 3, kick_peaks, (size_t)n_frames * kHipHopPeaks, outs, &dpeaks);
+    if (e) return e;
+  }
+  HipHopParams p = c->hiphop;
+  p.spec_stride = spec_stride;
+  p.f64 = f64 ? 1 : 0;
+  p.m = m;
+  p.audio_stride = audio_stride;
+  p.tw = it->second;
+  // one launch covers at most 2^30 workgroups (two per frame)
+  const int64_t per = (int64_t)1 << 29;
+  const size_t el = f64 ? 8 : 4;
+  for (int64_t f0 = 0; f0 < n_frames; f0 += per) {
+    HipHopParams q = p;
+    q.n_frames = std::min(per, n_frames - f0);
+    q.spec = dspec + f0 * spec_stride;
+    q.audio = static_cast<const char*>(daudio) + (size_t)(f0 * audio_stride) * el;
+    q.out = dout + f0 * kHipHopCols;
+    q.kick_peaks = dpeaks ? dpeaks + f0 * kHipHopPeaks : nullptr;
+    HIPC(c, launch_hiphop(q, c->stream));
+  }
   if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
   return 0;
 } catch (...) {

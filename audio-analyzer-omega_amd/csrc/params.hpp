@@ -533,6 +533,34 @@ struct GenreParams {
   int* peak_bins;           // [n_frames, kGenrePeaks] the largest peaks' bins, -1 past their number
 };
 
+// HipHopDetector.analyze (hiphop.hip; omega4/panels/hip_hop_detector.py:94-384): two workgroup roles per
+// frame (spectrum side, audio side) and a per-frame combine
+constexpr int kHipHopCols = 24;   // see include/omega.h for the columns
+constexpr int kHipHopThreads = 256;
+constexpr int kHipHopPeaks = 16;  // kept envelope peaks: floor((8192 - 3) / int(0.1 * 8000)) + 1 = 11 at the most
+constexpr int kHipHopMinRate = 8000;
+constexpr int kHipHopMinAudio = 64, kHipHopMaxAudio = 8192;
+// the contiguous bin ranges of the reference's masks over the increasing table: sub-bass [20, 60], bass
+// [60, 250], below Nyquist, low [20, 500], mid [500, 2000], high [2000, 8000], vocal [200, 3000], core
+// vocal [300, 2000], and every bin
+constexpr int kHipHopBands = 9;
+struct HipHopParams {
+  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values (|.| is taken)
+  int64_t spec_stride;
+  int n_bins;
+  const void* audio;        // frame f at audio + f * audio_stride, m samples (float32, or float64 when f64)
+  int f64;
+  int m;
+  int64_t audio_stride;
+  int64_t n_frames;
+  int band_lo[kHipHopBands], band_n[kHipHopBands];  // first bin and bin count of each range (0: no bins)
+  W64Stage sos[3][4];       // sub-bass, kick, hi-hat: four DF2T sections each (b0, b1, b2, a1, a2)
+  int distance;             // int(0.1 * sample_rate): find_peaks' distance on the kick envelope
+  const double2* tw;        // [m / 2 + 1] e^{-2 pi i q / m}
+  double* out;              // [n_frames, kHipHopCols]
+  int* kick_peaks;          // [n_frames, kHipHopPeaks] or nullptr
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

@@ -9,9 +9,10 @@ from .engine import DEFAULT_RESOLUTIONS, METER_KEYS, NORTHSTAR_RESOLUTIONS, Band
 from .pitch_detection import CepstralAnalyzer, PitchDetectionConfig, get_preset_config, list_presets
 from .harmonic_analysis import HarmonicAnalyzer, HarmonicMetrics
 from .genre_classification import GenreClassifier
+from .hip_hop_detector import HipHopDetector
 
 __all__ = [
-    "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier",
+    "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector",
     "LIB_PATH", "OmegaError", "UnsupportedError", "lib", "Engine", "Resolution", "BandTable",
     "DEFAULT_RESOLUTIONS", "NORTHSTAR_RESOLUTIONS", "METER_KEYS",
     "CepstralAnalyzer", "PitchDetectionConfig", "get_preset_config", "list_presets",

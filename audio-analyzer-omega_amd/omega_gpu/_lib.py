@@ -63,6 +63,10 @@ class GenreConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("n_bins", C.c_int32)]
 
 
+class HipHopConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("n_bins", C.c_int32)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -111,6 +115,12 @@ EXPORTS = {
     "omega_genre_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
     "omega_genre_reset": (C.c_int, [C.c_void_p]),
+    "omega_hiphop_config_default": (None, [C.POINTER(HipHopConfig)]),
+    "omega_hiphop_configure": (C.c_int, [C.c_void_p, C.POINTER(HipHopConfig), C.c_void_p]),
+    "omega_hiphop_get_sos": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "omega_hiphop_design_sos": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
+    "omega_hiphop_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

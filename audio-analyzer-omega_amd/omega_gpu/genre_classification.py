@@ -16,8 +16,9 @@ else the device's flatness value; the chroma Gini concentration, entropy and pow
 change rate and key stability. ``classify`` restates the pattern scoring, the per-genre modifiers, the
 3-deep history, the boosts and the softmax. The ``genre_patterns`` table is data the caller supplies
 (``GenreClassifier(fs, genre_patterns=reference.genre_patterns)``); without one ``classify`` raises. The
-reference's HipHopDetector is not built: pass its confidence as ``hip_hop_confidence`` or Hip-Hop is
-scored from its pattern row, as the reference does when classify gets no audio.
+reference's HipHopDetector is a facade of its own (omega_gpu.HipHopDetector): pass its confidence as
+``hip_hop_confidence`` or Hip-Hop is scored from its pattern row, as the reference does when classify gets
+no audio.
 
 There is no CPU fallback: a shape the library does not build (bins outside 16..8193, audio outside
 15..8192 samples) raises UnsupportedError with the library's message.

@@ -495,6 +495,65 @@ int omega_genre_features(omega_ctx* ctx, const float* spectra, int64_t spec_stri
                          int32_t m, int64_t audio_stride, int64_t n_frames, double* out, int32_t* peak_bins, int mem);
 int omega_genre_reset(omega_ctx* ctx);
 
+/* HipHopDetector.analyze (omega4/panels/hip_hop_detector.py:94-154 with the helpers it calls, :156-384) for
+ * n_frames independent frames: the float32 spectrum of n_bins values at spectra + f*spec_stride (its magnitude
+ * is taken) over the float64 frequency table given to omega_hiphop_configure, and the frame's m audio samples
+ * (float32, or float64 when f64 != 0: rms and energies then follow numpy's float64) at audio + f*audio_stride;
+ * rows may overlap. The reference filters every frame from the zero state, so the device keeps no state. The
+ * entry points are additive to ABI 5: a caller detects them by their presence.
+ * out [n_frames, OMEGA_HIPHOP_COLS] float64, in this order:
+ *    0 rms                      np.sqrt(np.mean(x ** 2)) in the audio's precision (float32: bit for bit)
+ *    1 sub_bass_presence        min(3 (0.3 t + 0.5 f + 0.2 min(s, 1)), 1): t the filtered RMS over rms (float64),
+ *                               f and s the float32 power ratios
+ *    2 kick_peak_count          find_peaks(|hilbert(kick band)|, height = mean + 1.5 std, distance = int(0.1 fs))
+ *    3 kick_pattern_factor      what multiplies the caller's kick magnitude: 0.6 regularity + 0.4 (1 - syncopation)
+ *                               of the peak spacings, 0.5 with at most one peak
+ *    4 hihat_zero_crossings     count of nonzero np.diff(np.sign(hi-hat band)) (the rate is this / m)
+ *    5 hihat_density            min(10 rate, 1) min(5 filtered RMS / rms, 1)
+ *    6 spectral_tilt            float32, operation for operation
+ *    7 vocal_peak_count         find_peaks(|spectrum[200..3000 Hz]|, prominence = float32(max * 0.3), distance = 20)
+ *    8 vocal_presence           float32, operation for operation
+ *    9 flags                    bit 0: silent (rms < 0.001, the reference's gate): every column but rms and
+ *                               flags is 0. bit 1: non-finite input (a sample or a bin): the whole row is 0;
+ *                               the other frames of the batch are unaffected
+ *   10 sub_bass_rms, 11 hihat_rms   np.sqrt(np.mean(.)) of the two filtered signals (float64)
+ *   12 envelope_threshold       mean + 1.5 np.std of the kick envelope
+ *   13 sub_bass_power [20, 60], 14 bass_power [60, 250], 15 total_power (freqs < fs / 2: the Nyquist bin is left
+ *      out), 16 low_energy [20, 500], 17 mid_energy [500, 2000], 18 high_energy [2000, 8000], 19 vocal_energy
+ *      [200, 3000], 20 core_vocal_energy [300, 2000], 21 total_energy (every bin): np.sum(np.abs(.) ** 2) over
+ *      the inclusive masks as numpy's float32 pairwise sums, bit for bit; 0 over a range without bins
+ *   22 tilt_branch              0: no tilt (an empty band or zero energy), 1: plain, 2: boosted (low_ratio > 0.5),
+ *                               3: boosted and clipped to 1
+ *   23 vocal_branch             0: no value (no vocal bins, zero energy, or <= 10 vocal bins), 1: float32 value,
+ *                               2: clipped to 1
+ * kick_peaks [n_frames, OMEGA_HIPHOP_PEAKS] int32 (may be NULL): the kept envelope peaks in index order, -1 past
+ * their number. The float64 columns that pass through the filters (1, 3, 5, 10-12) agree with scipy's sequential
+ * sosfilt to 1e-9 relative (a 256-chunk float64 scan); the integer columns and the float32-path columns are exact.
+ * kick_detected, the kick magnitude, the tempo stub, the confidence weights, the sub-genre and the 30-deep
+ * histories are scalar host work left to the caller (omega_gpu.HipHopDetector restates them).
+ * omega_hiphop_configure designs the three band-pass cascades (scipy.signal.butter(4, [lo, hi], 'bandpass',
+ * fs=fs, output='sos'): sub-bass 20-60 Hz, kick 40-100 Hz, hi-hat 3000-min(10000, 0.9 fs/2) Hz) and stores the
+ * masks' bin ranges; it must precede omega_hiphop_features and may be repeated with another table or rate.
+ * omega_hiphop_get_sos returns the configured sections of filter `which` (0 sub-bass, 1 kick, 2 hi-hat) as
+ * out[4][6] = b0 b1 b2 a0 a1 a2; omega_hiphop_design_sos designs them for a rate without a context.
+ * Supported: sample_rate >= 8000 Hz (OMEGA_HIPHOP_PEAKS covers the floor((8192 - 3) / 800) + 1 = 11 peaks that
+ * fit at that rate), 16 <= n_bins <= 8193, strictly increasing freqs, m a power of two 64..8192; other sizes
+ * return OMEGA_EUNSUP. */
+#define OMEGA_HIPHOP_COLS 24
+#define OMEGA_HIPHOP_PEAKS 16
+typedef struct {
+  int32_t sample_rate;
+  int32_t n_bins;                    /* entries of freqs and bins per spectrum */
+} omega_hiphop_config;
+/* 48000 Hz, 512 bins (the app's combined spectrum). */
+void omega_hiphop_config_default(omega_hiphop_config* cfg);
+int omega_hiphop_configure(omega_ctx* ctx, const omega_hiphop_config* cfg, const double* freqs);
+int omega_hiphop_get_sos(omega_ctx* ctx, int32_t which, double* out);
+int omega_hiphop_design_sos(int32_t sample_rate, int32_t which, double* out);
+int omega_hiphop_features(omega_ctx* ctx, const float* spectra, int64_t spec_stride, const void* audio, int32_t f64,
+                          int32_t m, int64_t audio_stride, int64_t n_frames, double* out, int32_t* kick_peaks,
+                          int mem);
+
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks
  * of chunk_size samples, s16 scaled by 1/32768), its per-chunk noise gate (:620-641: RMS, background
