@@ -23,6 +23,7 @@
 namespace omega {
 
 constexpr int kAnyThreads = 256;
+constexpr int kAnyF32Radix = 7;  // radices above it (the remaining primes) accumulate in float64
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -39,6 +40,20 @@ __device__ float2* any_fft(float2* a, float2* b, const AnyFftParams& p) {
       const int eq = (k + q * Ns) * step;  // < N
       float2 acc = make_float2(0.f, 0.f);
       int e = 0;
+      if (R > kAnyF32Radix) {
+        // a large prime factor: R terms summed one after the other lose up to R eps / 2 in float32 (coherent
+        // terms, e.g. the peak of a pulse: 5.9e-6 relative at R = 1021) -- float64 sums, rounded once
+        double ax = 0.0, ay = 0.0;
+        for (int r = 0; r < R; ++r) {
+          const float2 v = a[j + r * NR], w = p.tw[e];
+          ax += (double)v.x * w.x - (double)v.y * w.y;
+          ay += (double)v.x * w.y + (double)v.y * w.x;
+          e += eq;
+          if (e >= N) e -= N;
+        }
+        b[(j / Ns) * Ns * R + k + q * Ns] = make_float2((float)ax, (float)ay);
+        continue;
+      }
       for (int r = 0; r < R; ++r) {
         const float2 v = a[j + r * NR], w = p.tw[e];
         acc.x += v.x * w.x - v.y * w.y;
@@ -112,7 +127,7 @@ __global__ __launch_bounds__(kAnyThreads) void any_truepeak_kernel(AnyFftParams 
     __syncthreads();
   }
   mx = any_block_max(mx, red);
-  if (threadIdx.x == 0) p.tp_out[blockIdx.x] = mx < 1e-10f ? -100.0f : 20.0f * log10f(mx);
+  if (threadIdx.x == 0) p.tp_out[blockIdx.x] = tp_db(mx);
 }
 
 __global__ __launch_bounds__(kAnyThreads) void any_rfft_kernel(AnyFftParams p) {

@@ -8,6 +8,13 @@ namespace omega {
 constexpr int kMaxRes = 4;
 constexpr int kMaxLog2 = 15;  // twiddle tables for sizes 2^1 .. 2^14 (+1 spare)
 
+// True peak in dB of a frame's float32 peak (professional_meters.py:295-299): -100 below 1e-10, else
+// 20 log10(peak) rounded once to float32 (20.0f * log10f(peak) rounds twice: up to an ulp of the result
+// off for an exact peak). One lane per frame runs it.
+__device__ __forceinline__ float tp_db(float peak) {
+  return peak < 1e-10f ? -100.0f : (float)(20.0 * log10((double)peak));
+}
+
 // One resolution of the multi-resolution FFT (FFTConfig, multi_resolution_fft.py:26-44).
 // One combine entry. tm = t | op << 24 with op 0: store, 1: add (a later owner of t), 2: store 0
 // (no owner). Entries of a resolution are contiguous; owners of one target run in resolution order.

@@ -213,7 +213,7 @@ __device__ __forceinline__ void truepeak_rf_body(const SpectralParams& p, int64_
   }
   const float peak = block_max<NTH>(fmaxf(mx, fmx * (0.5f / K)), red, tid);
   if (tid == 0) {
-    const float db = peak < 1e-10f ? -100.0f : 20.0f * log10f(peak);
+    const float db = tp_db(peak);
     if (p.tp_done) {  // write-through, drained, then counted in (see SpectralParams::tp_done)
       __hip_atomic_store(reinterpret_cast<unsigned*>(p.tp_out + cf), __float_as_uint(db), __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
