@@ -56,6 +56,7 @@ hipError_t launch_pitch(const PitchParams& p, hipStream_t s);
 hipError_t launch_harmonic(const HarmonicParams& p, hipStream_t s);
 hipError_t launch_genre(const GenreParams& p, hipStream_t s);
 hipError_t launch_hiphop(const HipHopParams& p, hipStream_t s);
+hipError_t launch_phase(const PhaseParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -459,6 +460,11 @@ struct omega_ctx {
   HipHopParams hiphop{};
   double hiphop_sos[3][4][6] = {};
   std::map<int, double2*> hiphop_tw;
+  // stereo phase correlation (omega_phase_configure / omega_phase_correlation): the configuration with the
+  // band ranges (no frame state) and per frame length the twiddle table and np.hanning
+  bool phase_set = false;
+  PhaseParams phase{};
+  std::map<int, std::pair<double2*, double*>> phase_tabs;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables
@@ -2638,6 +2644,131 @@ int omega_hiphop_features(omega_ctx* c, const float* spectra, int64_t spec_strid
     q.out = dout + f0 * kHipHopCols;
     q.kick_peaks = dpeaks ? dpeaks + f0 * kHipHopPeaks : nullptr;
     HIPC(c, launch_hiphop(q, c->stream));
+  }
+  if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+void omega_phase_config_default(omega_phase_config* cfg) {
+  if (!cfg) return;
+  *cfg = omega_phase_config{};
+  cfg->sample_rate = 48000;
+  cfg->m = 2048;
+}
+
+namespace {
+// np.hanning(m) by numpy's own route, 0.5 + 0.5 cos(pi k / (m - 1)) over k = 1 - m, 3 - m, ..., m - 1
+void phase_hanning(int m, double* out) {
+  for (int n = 0; n < m; ++n) out[n] = 0.5 + 0.5 * std::cos(M_PI * (double)(2 * n + 1 - m) / (double)(m - 1));
+}
+}  // namespace
+
+int omega_phase_hanning(int32_t m, double* out) try {
+  if (!out || m < 2) return OMEGA_EINVAL;
+  phase_hanning(m, out);
+  return 0;
+} catch (...) {
+  return guard_fail(nullptr);
+}
+
+int omega_phase_band_ranges(int32_t sample_rate, int32_t m, const double* edges, int32_t* ranges) try {
+  if (!edges || !ranges || sample_rate <= 0 || m < 2) return OMEGA_EINVAL;
+  for (int i = 0; i <= kPhaseBands; ++i)
+    if (!std::isfinite(edges[i])) return OMEGA_EINVAL;
+  // np.fft.rfftfreq(m, 1 / fs) in its own arithmetic: val = 1.0 / (m * d), f_k = k * val. The table increases,
+  // so the mask (freqs >= lo) & (freqs < hi) is one range.
+  const double d = 1.0 / (double)sample_rate, val = 1.0 / ((double)m * d);
+  const int nb = m / 2 + 1;
+  for (int b = 0; b < kPhaseBands; ++b) {
+    int lo = 0, n = 0;
+    for (int k = 0; k < nb; ++k) {
+      const double f = (double)k * val;
+      if (f >= edges[b] && f < edges[b + 1]) {
+        if (!n) lo = k;
+        ++n;
+      }
+    }
+    ranges[2 * b] = lo;
+    ranges[2 * b + 1] = lo + n;
+  }
+  return 0;
+} catch (...) {
+  return guard_fail(nullptr);
+}
+
+int omega_phase_configure(omega_ctx* c, const omega_phase_config* cfg, const double* edges) try {
+  if (!c || !cfg) return OMEGA_EINVAL;
+  if (!edges) return fail(c, OMEGA_EINVAL, "phase: edges is NULL");
+  if (cfg->sample_rate <= 0) return fail(c, OMEGA_EINVAL, "phase: need sample_rate > 0");
+  const int m = cfg->m;
+  if (m <= 0) return fail(c, OMEGA_EINVAL, "phase: frame length %d", m);
+  if (!is_pow2_in(m, kPhaseMinFrame, kPhaseMaxFrame))
+    return fail(c, OMEGA_EUNSUP, "phase: %d samples per frame (the powers of two %d..%d are built)", m, kPhaseMinFrame,
+                kPhaseMaxFrame);
+  int32_t ranges[2 * kPhaseBands];
+  if (omega_phase_band_ranges(cfg->sample_rate, m, edges, ranges))
+    return fail(c, OMEGA_EINVAL, "phase: the band edges must be finite");
+  HIPC(c, hipSetDevice(c->device));
+  auto it = c->phase_tabs.find(m);
+  if (it == c->phase_tabs.end()) {
+    std::vector<double2> tw((size_t)m / 2);
+    for (int q = 0; q < m / 2; ++q) tw[q] = make_double2(std::cos(2 * M_PI * q / m), -std::sin(2 * M_PI * q / m));
+    std::vector<double> win((size_t)m);
+    phase_hanning(m, win.data());
+    double2* d1 = nullptr;
+    double* d2 = nullptr;
+    int e = upload(c, &d1, tw);
+    if (!e) e = upload(c, &d2, win);
+    if (e) return e;
+    it = c->phase_tabs.emplace(m, std::make_pair(d1, d2)).first;
+  }
+  PhaseParams p{};
+  p.m = m;
+  while ((1 << p.bits) < m) ++p.bits;
+  for (int b = 0; b < kPhaseBands; ++b) p.first[b] = ranges[2 * b], p.last[b] = ranges[2 * b + 1];
+  p.tw = it->second.first;
+  p.hann = it->second.second;
+  c->phase = p;
+  c->phase_set = true;
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_phase_correlation(omega_ctx* c, const void* left, const void* right, int32_t f64, int64_t frame_stride,
+                            int64_t n_frames, double* out, double* points, int mem) try {
+  if (!c || !out) return OMEGA_EINVAL;
+  if (!c->phase_set) return fail(c, OMEGA_EINVAL, "phase: omega_phase_configure has not been called");
+  if (!left || !right || n_frames < 0 || frame_stride < 1) return fail(c, OMEGA_EINVAL, "phase: bad frame layout");
+  if (n_frames == 0) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  const int m = c->phase.m;
+  const size_t el = f64 ? 8 : 4;
+  std::vector<HostOut> outs;
+  const void *dl = left, *dr = right;
+  double *dout = out, *dpts = points;
+  if (mem == OMEGA_MEM_HOST) {
+    const size_t span = (size_t)((n_frames - 1) * frame_stride + m) * el;
+    int e = stage_in(c, 0, left, span, &dl);
+    if (!e) e = stage_in(c, 1, right, span, &dr);
+    if (!e) e = stage_out(c, 2, out, (size_t)n_frames * kPhaseCols, outs, &dout);
+    if (!e) e = stage_out(c, 3, points, (size_t)n_frames * kPhasePoints * 2, outs, &dpts);
+    if (e) return e;
+  }
+  // one launch covers at most 2^30 workgroups
+  const int64_t per = (int64_t)1 << 30;
+  for (int64_t f0 = 0; f0 < n_frames; f0 += per) {
+    PhaseParams q = c->phase;
+    q.f64 = f64 ? 1 : 0;
+    q.frame_stride = frame_stride;
+    q.n_frames = std::min(per, n_frames - f0);
+    q.left = static_cast<const char*>(dl) + (size_t)(f0 * frame_stride) * el;
+    q.right = static_cast<const char*>(dr) + (size_t)(f0 * frame_stride) * el;
+    q.out = dout + f0 * kPhaseCols;
+    q.points = dpts ? dpts + f0 * kPhasePoints * 2 : nullptr;
+    HIPC(c, launch_phase(q, c->stream));
   }
   if (mem == OMEGA_MEM_HOST) return finish_host(c, outs);
   return 0;

@@ -568,6 +568,27 @@ struct HipHopParams {
   int* kick_peaks;          // [n_frames, kHipHopPeaks] or nullptr
 };
 
+// PhaseCorrelationPanel's analysis (phase.hip; omega4/panels/phase_correlation.py:124-220) on real stereo
+// frames: one workgroup per frame
+constexpr int kPhaseCols = 17;    // see include/omega.h for the columns
+constexpr int kPhaseBands = 10;
+constexpr int kPhasePoints = 128;  // ceil(m / max(1, m / 100)) is 128 at m = 128 and 256, less elsewhere
+constexpr int kPhaseThreads = 256;
+constexpr int kPhaseMinFrame = 64, kPhaseMaxFrame = 8192;
+struct PhaseParams {
+  const void* left;         // frame f at left + f * frame_stride and right + f * frame_stride, m samples each
+  const void* right;
+  int64_t frame_stride;
+  int64_t n_frames;
+  int f64;                  // the samples are float64 (else float32, widened on load)
+  int m, bits;              // m = 1 << bits
+  int first[kPhaseBands], last[kPhaseBands];  // the masks' bin ranges [first, last) (equal: no bins)
+  const double* hann;       // [m] np.hanning(m)
+  const double2* tw;        // [m / 2] e^{-2 pi i q / m}
+  double* out;              // [n_frames, kPhaseCols]
+  double* points;           // [n_frames, kPhasePoints, 2] or nullptr
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

@@ -10,9 +10,10 @@ from .pitch_detection import CepstralAnalyzer, PitchDetectionConfig, get_preset_
 from .harmonic_analysis import HarmonicAnalyzer, HarmonicMetrics
 from .genre_classification import GenreClassifier
 from .hip_hop_detector import HipHopDetector
+from .phase_correlation import PhaseCorrelation
 
 __all__ = [
-    "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector",
+    "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector", "PhaseCorrelation",
     "LIB_PATH", "OmegaError", "UnsupportedError", "lib", "Engine", "Resolution", "BandTable",
     "DEFAULT_RESOLUTIONS", "NORTHSTAR_RESOLUTIONS", "METER_KEYS",
     "CepstralAnalyzer", "PitchDetectionConfig", "get_preset_config", "list_presets",

@@ -67,6 +67,10 @@ class HipHopConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("n_bins", C.c_int32)]
 
 
+class PhaseConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_int32), ("m", C.c_int32)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -121,6 +125,12 @@ EXPORTS = {
     "omega_hiphop_design_sos": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
     "omega_hiphop_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
+    "omega_phase_config_default": (None, [C.POINTER(PhaseConfig)]),
+    "omega_phase_band_ranges": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "omega_phase_hanning": (C.c_int, [C.c_int32, C.c_void_p]),
+    "omega_phase_configure": (C.c_int, [C.c_void_p, C.POINTER(PhaseConfig), C.c_void_p]),
+    "omega_phase_correlation": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

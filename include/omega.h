@@ -554,6 +554,59 @@ int omega_hiphop_features(omega_ctx* ctx, const float* spectra, int64_t spec_str
                           int32_t m, int64_t audio_stride, int64_t n_frames, double* out, int32_t* kick_peaks,
                           int mem);
 
+/* PhaseCorrelationPanel's analysis (omega4/panels/phase_correlation.py:124-220: _calculate_correlation, the
+ * balance lines, _update_goniometer_enhanced, _calculate_band_correlations) for n_frames independent stereo
+ * frames of m samples: frame f is at left + f*frame_stride and right + f*frame_stride, in elements (float32, or
+ * float64 when f64 != 0; float32 is widened on load and everything downstream is float64). The planar
+ * [F, 2, m] batch is right = left + m, frame_stride = 2m; rows may overlap. The reference's update() fabricates
+ * its right channel from a mono frame with np.random; here both channels are the caller's. The device keeps no
+ * state. The entry points are additive to ABI 5: a caller detects them by their presence.
+ * out [n_frames, OMEGA_PHASE_COLS] float64, in this order:
+ *    0 correlation      clip(mean(ln rn) / (std_l std_r), -1, 1) of the mean-centred channels (two passes: the
+ *                       means, then the centred sums); 0.0 when a std is 0
+ *    1 stereo_width     1 - |correlation|
+ *    2 balance          (rms_right - rms_left) / (rms_right + rms_left); 0 when the sum is 0 (flag bit 1)
+ *    3 rms_left, 4 rms_right   sqrt(mean(x^2))
+ *    5 flags            bit 0: a non-finite sample in either channel: the whole row and the frame's points are
+ *                       0; the other frames of the batch are unaffected. bit 1: rms_left + rms_right == 0 (the
+ *                       reference leaves its balance untouched). bit 2: a time-domain std was 0 (the
+ *                       reference's 0.0 fallback)
+ *    6 band mask        bit b set: band b has at least one bin (the reference leaves the others untouched)
+ *    7..16 band correlations   the same clipped correlation of |rfft(l np.hanning(m))| and |rfft(r np.hanning(m))|
+ *                       over the bins with edges[b] <= f_k < edges[b + 1]; 0.0 for a band of one bin (its centred
+ *                       values are 0) and for a band without bins
+ * points [n_frames, OMEGA_PHASE_POINTS, 2] float64 (may be NULL): the goniometer's (x, y) of the samples
+ * 0, step, 2 step, ... < m with step = max(1, m / 100), in the reference's operation order (bit for bit); 0 past
+ * their number ceil(m / step).
+ * Columns 0-2 and 7-16 agree with the reference called on float64 arrays to 1e-9 absolute, the RMS columns to
+ * 1e-9 relative, on frames whose stds keep the margins tests/golden/gen_phase.py asserts (one m-point float64
+ * transform of l w + i r w and lane-strided sums stand for numpy's two rffts and pairwise sums; the shared
+ * transform leaves about 1e-16 of the louder channel's magnitudes in the other's bins, so an exactly silent
+ * channel is given its exact zero spectrum and a channel some 200 dB below the other is not resolved).
+ * omega_phase_band_ranges (no context, no device) turns the masks over np.fft.rfftfreq(m, 1 / sample_rate), in
+ * numpy's own arithmetic (val = 1.0 / (m * (1.0 / fs)), f_k = k * val), into ranges[10][2] = [first, last);
+ * first == last: no bins. edges are the caller's 11 band edges (the reference's np.logspace(log10(20),
+ * log10(min(20000, fs / 2)), 11)); they are not recomputed here, because at 16000 Hz one ulp of the top edge
+ * decides whether the Nyquist bin belongs to band 9. omega_phase_hanning writes np.hanning(m) as the library
+ * computes and uploads it (numpy's route 0.5 + 0.5 cos(pi k / (m - 1)), k = 1 - m, 3 - m, ...), m >= 2.
+ * omega_phase_configure stores the ranges and uploads the tables; it must precede omega_phase_correlation and
+ * may be repeated. Supported: m a power of two 64..8192 (16 bytes of LDS per sample); other sizes return
+ * OMEGA_EUNSUP. */
+#define OMEGA_PHASE_BANDS 10
+#define OMEGA_PHASE_COLS 17
+#define OMEGA_PHASE_POINTS 128 /* max over supported m of ceil(m / max(1, m / 100)) */
+typedef struct {
+  int32_t sample_rate;
+  int32_t m;                         /* samples per frame and channel */
+} omega_phase_config;
+/* 48000 Hz, 2048 samples. */
+void omega_phase_config_default(omega_phase_config* cfg);
+int omega_phase_band_ranges(int32_t sample_rate, int32_t m, const double* edges, int32_t* ranges);
+int omega_phase_hanning(int32_t m, double* out);
+int omega_phase_configure(omega_ctx* ctx, const omega_phase_config* cfg, const double* edges);
+int omega_phase_correlation(omega_ctx* ctx, const void* left, const void* right, int32_t f64, int64_t frame_stride,
+                            int64_t n_frames, double* out, double* points, int mem);
+
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks
  * of chunk_size samples, s16 scaled by 1/32768), its per-chunk noise gate (:620-641: RMS, background
