@@ -1,0 +1,1120 @@
+// libomega.so host side: the batch launch path -- omega_process_frames down to launch_batch, with the
+// meter segments, the counters and the stream layout -- and the meter, true-peak and weighting entry
+// points that share its state. The per-step path is whole in this translation unit.
+
+#include "host.hpp"
+
+namespace {
+
+constexpr int kChunkFrames = kMeterChunk;
+constexpr int kBatchWaves = 8;  // waves of a batch_kernel workgroup (rfkern.hip kBatchThreads / 64)
+// meter workgroups of the batch grid at most: they wait (spinning) for the meter prep kernel, which
+// may be dispatched after them and needs a CU with at most one batch workgroup resident (1024 threads
+// and 72.6 KiB of LDS beside one 512-thread, 71.9 KiB batch workgroup). 64 waiting workgroups hold at
+// most 64 of the 512 batch slots, so at least 192 CUs keep a slot that other roles free as they
+// finish. (Round 1: one meter workgroup per 8 outputs of a 4096-frame batch took every slot and waited
+// until the poll bound expired.)
+#ifndef OMEGA_METER_WGS
+#define OMEGA_METER_WGS 64  // (measured: 16 and 32 slower, profiles/r04_ab_meter_wgs.txt)
+#endif
+constexpr int kMeterWgs = OMEGA_METER_WGS;
+
+int get_kw_tab(omega_ctx* c, int M, int L, BiquadTab** out) {
+  const auto key = std::make_pair(M, L);
+  auto it = c->kw_tabs.find(key);
+  if (it != c->kw_tabs.end()) {
+    *out = it->second;
+    return 0;
+  }
+  const double fs = c->cfg.sample_rate;
+  std::vector<BiquadTab> t = {make_biquad_tab(butter2(38.0, fs, true), L),
+                              make_biquad_tab(butter2(1500.0, fs, true), L)};
+  BiquadTab* d = nullptr;
+  int r = upload(c, &d, t);
+  if (r) return r;
+  c->kw_tabs[key] = d;
+  *out = d;
+  return 0;
+}
+int get_kw_tab(omega_ctx* c, int M, BiquadTab** out) { return get_kw_tab(c, M, kw_chunk(M), out); }
+
+// True-peak kernel choice: the register-FFT kernel for 8192- and 16384-sample frames, the LDS-pass
+// kernel for the other powers of two.
+hipError_t tp_launch(omega_ctx* c, int W, const SpectralParams& sp, hipStream_t s) {
+  (void)c;
+  if (W == 16384 || W == 8192) return launch_truepeak_rf(W, sp, s);
+  return launch_truepeak(W, sp, s);
+}
+
+SpectralParams spectral_params(omega_ctx* c) {
+  SpectralParams p{};
+  p.tp_phases = 0xE;
+  p.C = c->cfg.n_channels;
+  p.n_res = c->cfg.n_res;
+  p.rf_sizes = c->rf_sizes;
+  for (int r = 0; r < p.n_res; ++r) {
+    ResParam& q = p.res[r];
+    q.n = c->cfg.res[r].fft_size;
+    q.offset = c->cfg.frame_size - q.n;
+    q.win = c->d_win[r];
+    q.wgt = c->d_wgt[r];
+    q.ent_begin = c->ent_begin[r];
+    q.ent_end = c->ent_end[r];
+    q.cw = (float)c->cfg.res[r].weight;
+    q.low_band = c->ent_jmax[r] < 256;
+    q.pair_lo = c->pair_lo[r];
+    q.pair_hi = c->pair_hi[r];
+  }
+  p.ent = c->d_ent;
+  p.T = c->cfg.target_bins;
+  p.rot = c->d_rot;
+  for (int l = 0; l < kMaxLog2; ++l) p.tw[l] = c->d_tw[l];
+  return p;
+}
+
+bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+// Meter aggregates over n_frames x C values, in chunks of at most kChunkFrames frames; each chunk
+// reads the state buffers `cur` and writes `cur ^ 1`.
+std::vector<MeterPrepParams> meter_chunks(omega_ctx* c, const float* lufs, const float* tp, int64_t n_frames,
+                                          double* out) {
+  const int C = c->cfg.n_channels;
+  std::vector<MeterPrepParams> v;
+  for (int64_t f0 = 0; f0 < n_frames; f0 += kChunkFrames) {
+    const int64_t nf = std::min<int64_t>(kChunkFrames, n_frames - f0);
+    const int a = c->cur, b = c->cur ^ 1;
+    MeterPrepParams p{};
+    p.lufs = lufs + f0 * C;
+    p.tp = tp + f0 * C;
+    p.n_frames = nf;
+    p.C = C;
+    p.hist_l_in = c->d_hist_l[a];
+    p.hist_t_in = c->d_hist_t[a];
+    p.n_l_in = c->d_nl[a];
+    p.n_t_in = c->d_nt[a];
+    p.skeys_in = c->d_skeys[a];
+    p.n_s_in = c->d_ns[a];
+    p.t0_in = c->d_t0[a];
+    p.hist_l_out = c->d_hist_l[b];
+    p.hist_t_out = c->d_hist_t[b];
+    p.n_l_out = c->d_nl[b];
+    p.n_t_out = c->d_nt[b];
+    p.skeys_out = c->d_skeys[b];
+    p.n_s_out = c->d_ns[b];
+    p.t0_out = c->d_t0[b];
+    p.HL = c->HL;
+    p.HT = c->HT;
+    p.mom_len = c->cfg.momentary_len;
+    p.short_len = c->cfg.short_len;
+    p.int_len = c->cfg.integrated_len;
+    p.peak_len = c->cfg.peak_len;
+    p.poll_limit = c->poll_limit;
+    p.err_word = c->d_err;
+    p.gate = (float)c->cfg.gate_lufs;
+    p.core = c->d_core[a];
+    p.ext = c->d_ext[a];
+    p.n_core = c->d_ncore[a];
+    p.n_ext = c->d_next[a];
+    p.gcount = c->d_gcount[a];
+    p.gsum = c->d_gsum[a];
+    p.out = out + f0 * C * OMEGA_N_METERS;
+    p.parts = 3;
+    p.seg_ctr = c->d_kw_done + 4;
+    p.seg_pre_target = c->seg_par[a];
+    p.seg_post_target = c->seg_par[b];
+    v.push_back(p);
+    c->cur = b;
+  }
+  return v;
+}
+
+// All meter chunks on one stream. tp_ready: when set, an event the true peaks of the batch wait on
+// (the prep kernels only read the LUFS_inst values, so they may start before it).
+int meters_enqueue(omega_ctx* c, const float* lufs, const float* tp, int64_t n_frames, double* out,
+                   hipStream_t stream, hipEvent_t tp_ready, unsigned* wait_ctr = nullptr, unsigned wait_target = 0) {
+  bool first = true;
+  for (MeterPrepParams p : meter_chunks(c, lufs, tp, n_frames, out)) {
+    // (wait_ctr: the first chunk's prep polls it before reading the batch's values -- the true peaks
+    // of omega_calculate_lufs on the side stream counting in, instead of an event join)
+    if (first && wait_ctr) {
+      p.wait_ctr = wait_ctr;
+      p.wait_target = wait_target;
+    }
+    HIPC(c, launch_meter_prep(p, stream));
+    if (tp_ready && first) HIPC(c, hipStreamWaitEvent(stream, tp_ready, 0));
+    HIPC(c, launch_meter_query(p, stream));
+    first = false;
+  }
+  return 0;
+}
+
+// Overlapped pipelined batches: order the last call's batch stream (batch, then meter segment) into the
+// context's stream. (The call before it was joined when the last one was enqueued.)
+int join_batches(omega_ctx* c) {
+  if (!c->unjoined) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  HIPC(c, hipStreamWaitEvent(c->stream, c->ev_done[c->last_bs], 0));
+  c->unjoined = false;
+  c->prev_span.clear();
+  return 0;
+}
+
+}  // namespace
+
+// Meter pipelining: the pending meter segment as a launch of its own on the context's stream (the
+// stream of the batch it belongs to: omega_set_stream flushes before switching), or on `on` (an
+// overlapped call's batch stream); an overlapped call still on its batch stream is joined first.
+namespace omega_host __attribute__((visibility("hidden"))) {
+int flush_meters(omega_ctx* c, hipStream_t on) {
+  if (!on)
+    if (int e = join_batches(c)) return e;
+  if (!c->pend) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  BatchPlan bp{};
+  bp.q_begin = 0;
+  bp.q_n = c->pend_nq;
+  bp.seg_start[0] = bp.seg_start[1] = bp.multi_start = c->pend_nq;  // (no other workgroups)
+  SpectralParams sp{};
+  KWeightParams kp{};
+  const hipError_t le = launch_batch(sp, kp, bp, c->pend_mq, c->pend_nq, on ? on : c->stream);
+  if (le != hipSuccess) return fail(c, OMEGA_EHIP, "meter segment launch: %s", hipGetErrorString(le));
+  c->pend = false;
+  c->seg_par[c->pend_par] = c->seg_issued + (unsigned)c->pend_nq;
+  c->seg_issued += (unsigned)c->pend_nq;
+  return 0;
+}
+}  // namespace omega_host
+
+namespace {
+
+// The signal-memory word of omega_ctx::d_tail, on first use (tail_ok: 1 ready, -1 no stream-wait-value
+// support on this device).
+int tail_init(omega_ctx* c) {
+  if (c->tail_ok != 0) return 0;
+  int ok = 0;
+  HIPC(c, hipDeviceGetAttribute(&ok, hipDeviceAttributeCanUseStreamWaitValue, c->device));
+  c->tail_ok = -1;
+  if (ok && hipExtMallocWithFlags(reinterpret_cast<void**>(&c->d_tail), 8, hipMallocSignalMemory) == hipSuccess) {
+    HIPC(c, hipMemset(c->d_tail, 0, 8));
+    c->tail_issued = 0;
+    c->tail_ok = 1;
+  }
+  return 0;
+}
+
+// Layout 3 applies to 16384-sample frames on direct launches (a captured graph would freeze the
+// kw_done target) when every requested stage has a 512-thread batch role: the register-FFT true peak,
+// at most one 16384-point resolution (on the register FFT), the others at most 8192 points, and
+// resolutions that commute (no combine target with several owners). *mr: the 16384-point resolution.
+bool batch_eligible(omega_ctx* c, const SpectralParams& sp, const KWeightParams& kp, int W, bool do_res, hipStream_t s,
+                    int* mr) {
+  *mr = -1;
+  if (W != 16384 || (c->cap && s == c->cap)) return false;  // (graph capture: the other layout)
+  if ((kp.lufs_out || kp.weighted_out) && kp.mode != 0) return false;
+  if (!do_res) return true;
+  if (!c->res_independent) return false;
+  for (int r = 0; r < sp.n_res; ++r) {
+    if (!sp.comb_out && !sp.res[r].mag_out) continue;
+    const int n = sp.res[r].n;
+    if (n == 16384) {
+      if (*mr >= 0 || !((sp.rf_sizes >> 14) & 1)) return false;
+      *mr = r;
+    } else if (n < 512 || n > 8192) {
+      return false;
+    }
+  }
+  return true;
+}
+
+// The default layout for 16384-sample frames. On `s`: one batch_kernel launch (BatchPlan: K-weighting
+// and 16384-point-resolution workgroups mixed, then the true peaks, then the small resolutions, then --
+// for a batch of at most kChunkFrames frames per channel -- the meter aggregates as the grid's last
+// segment; pipelined, the previous call's, between the true peaks and the small resolutions). On
+// fork[0]: the meter prep (it waits on the K-weighting count, kw_done, and counts itself
+// in). The meter workgroups wait for the prep's count and for the true peaks' count, so `s` completes
+// only after fork[0]'s work: no stream events and no kernel after the batch (each event record / wait
+// cost ~7-13 us of idle GPU between kernels). Longer batches (chunks chained through the per-context
+// scratch) keep the meter query kernels: the LUFS query on fork[0] counting itself in, the true-peak
+// query after the batch on `s` joining that count. Mixing the latency-bound K-weighting scans with
+// transform work is what pays (K-weighting alone 25.7 us, the true peak 37, the resolutions 26.5; one
+// batch launch of all three 73.9). Measured and rejected on MI355X (rounds 1-3): other role
+// orders (K-weighting as its own kernel 110.4 us per step; mixed with the true peaks 85.2; the true
+// peaks first ~equal; role chunks of one workgroup per CU), the meter queries after the batch (88 vs
+// 81-82), the true-peak query on the side stream joined in the batch's last workgroup (85-87), the
+// true-peak meter as a batch role (86-88), the true-peak meter by the batch's last true-peak workgroup,
+// joined there (86.2 vs 81.1, round 3). The in-grid meter segment measured even with the query kernels
+// (step 79.4-80.6 vs 79.0-79.4 us) at two fewer launches per call (host enqueue 13-17 vs 22-27 us).
+int enqueue_batch(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int64_t n_frames, const float* lufs,
+                  const float* tp, double* meters, hipStream_t s, int mr, bool do_tp, bool do_kw, bool fold) {
+  (void)W;
+  const int64_t n = sp.n_cf;
+  BatchPlan bp{};
+  int seg[2][3], ns[2] = {0, 0};
+  auto add = [&](int sg, int role, bool on) {
+    if (on) seg[sg][ns[sg]++] = role;
+  };
+  // (measured: the true peaks in segment 0 beside the K-weighting, the 16384-point resolution in
+  // segment 1, with or without the small resolutions before it: step 73.5-75.1 vs 68.8-70.5 us)
+  // (measured, round 5, pipelined step on one box: the K-weighting beside the true peaks with the
+  // 16384-point resolution after them, or the true peaks beside the 16384-point resolution with the
+  // K-weighting after them, 65.3-67.3 us against 65.3-67.1 for this order: the same)
+  add(0, 0, do_kw);        // segment 0: K-weighting and the 16384-point resolution, groups of 8 frames
+  add(0, 2, mr >= 0);
+  add(1, 1, do_tp);        // segment 1: the true peaks
+  const int64_t groups = (n + 7) / 8;
+  int64_t end = 0;
+  for (int sg = 0; sg < 2; ++sg) {
+    bp.n_roles[sg] = ns[sg] ? ns[sg] : 1;
+    for (int i = 0; i < 3; ++i) bp.roles[sg][i] = i < ns[sg] ? seg[sg][i] : 0;
+    end += ns[sg] ? 8 * ns[sg] * groups : 0;
+    if (end > 0x7FFFFFFF) return fail(c, OMEGA_EINVAL, "batch of %lld channel-frames too large", (long long)n);
+    bp.seg_begin[sg + 1] = (int)end;
+  }
+  bp.mr_res = mr < 0 ? 0 : mr;
+  int64_t nwg = 0;
+  for (int r = 0; r < sp.n_res; ++r) {
+    if (r == mr || (!sp.comb_out && !sp.res[r].mag_out)) continue;
+    const int K = sp.res[r].n / 2;
+    const int G = K / 16 < 64 ? 64 : K / 16;  // threads_for<K>() for K <= 4096
+    const int fpw = 512 / G;
+    bp.multi.res[bp.multi.n_seg] = r;
+    bp.multi.wg_begin[bp.multi.n_seg] = (int)nwg;
+    ++bp.multi.n_seg;
+    nwg += (n + fpw - 1) / fpw;
+  }
+  // the meter aggregates of a one-chunk batch as the grid's last segment (batch_meter_role): the prep
+  // kernel on fork[0] (it waits for the K-weighting count) counts itself in, the true-peak workgroups
+  // count themselves in, the meter workgroups wait for both; longer batches chain their chunks through
+  // the per-context scratch and keep the query kernels
+  const bool in_grid = meters && do_tp && do_kw && n_frames > 0 && n_frames <= kChunkFrames;
+  const int64_t n_mq = in_grid ? std::min<int64_t>((n + kBatchWaves - 1) / kBatchWaves, kMeterWgs) : 0;
+  // meter pipelining (fold): this launch runs the PREVIOUS call's meter segment as its last workgroups
+  // (its inputs are complete: that batch ended before this one starts; the prep that reads this batch's
+  // values still runs beside it on the side stream) and leaves its own pending
+  fold = fold && in_grid;
+  const int64_t q_n = fold ? (c->pend ? c->pend_nq : 0) : n_mq;
+  // grid order: segment 0 | segment 1 | small resolutions (measured: the small resolutions between the
+  // segments, step 80.4-81.3 vs 76.6-77.5 us, round 4); segment 0 in the period-8 role order
+  // (BatchPlan::pat: batch kernel 65.7-66.1 vs 70.9-71.5 us)
+  bp.pat = 1;
+  bp.multi_n = (int)nwg;
+  bp.seg_start[0] = 0;
+  bp.seg_start[1] = bp.seg_begin[1];
+  bp.multi_start = bp.seg_begin[2];
+  const int64_t body_end = end + nwg;
+  // the grid's last segment unpipelined (measured: placed before the small resolutions it holds 64
+  // slots from ~50 us on while it waits and the step is no shorter, 77.4-79.2 vs 77.0-78.0 us);
+  // pipelined, it waits for nothing (first in the grid it delayed the true peaks: step 68-69 vs 64-65
+  // us without meters)
+  bp.q_begin = (int)body_end;
+  bp.q_n = (int)q_n;
+  // pipelined (the previous call's segment: it waits for nothing), the segment goes after the true peaks
+  // and before the small resolutions instead: longest-first in the tail, its ~9-10 us workgroups ahead
+  // of the 7-12 us resolution ones (pipelined step 63.5-64.4 vs 64.9-65.2 us last, four alternations on
+  // one box, tools/ab.sh, outputs bitwise equal direct and pipelined; on a second box 62.8-64.7 vs
+  // 64.6-65.1 last and 62.8-64.4 after the 8192-point resolution).
+  // Unpipelined it stays last: before the small resolutions its waiting workgroups cost the in-call
+  // step 70.4-73.1 vs 66.9-67.6 us
+  if (fold) bp.q_begin = bp.multi_start;
+  // (measured, round 5: the pipelined segment between segment 0 and the true peaks instead, step
+  // 65.3-67.1 vs 66.5-66.6 us on one box: no difference)
+  const int64_t grid = body_end + q_n;
+  if (grid > 0x7FFFFFFF) return fail(c, OMEGA_EINVAL, "batch of %lld channel-frames too large", (long long)n);
+  MeterPrepParams mq{};
+  std::vector<MeterPrepParams> mc;
+  if (in_grid) {
+    const int a = c->cur;
+    const unsigned seg_par_was = c->seg_par[a ^ 1];
+    // the pending segment (parity a ^ 1) is enqueued by this launch: the prep's target for the state it
+    // reads (meter_chunks) counts it
+    if (fold && c->pend) c->seg_par[c->pend_par] = c->seg_issued + (unsigned)c->pend_nq;
+    const int cur_was = c->cur;  // (meter_chunks flips the state parity)
+    mc = meter_chunks(c, lufs, tp, n_frames, meters);
+    // the prep on the side stream, waiting for this batch's K-weighting count
+    MeterPrepParams p = mc[0];
+    p.q_done = c->d_kw_done + 3;
+    // pipelined: the prep polls generation-tagged words the K-weighting workgroups store without a
+    // drain or a count; unpipelined: the count
+    const size_t mir_n = (size_t)kChunkFrames * c->cfg.n_channels;
+    if (fold && !c->d_mirror) {
+      HIPC(c, hipMalloc(&c->d_mirror, 2 * mir_n * sizeof(unsigned long long)));
+      HIPC(c, hipMemset(c->d_mirror, 0, 2 * mir_n * sizeof(unsigned long long)));
+    }
+    const bool mirror = fold;
+    const unsigned gen_was = c->mirror_gen;
+    if (mirror) {
+      // consecutive launches alternate parity: a prep still reading one parity while the next launch's
+      // K-weighting writes the other (it waits for nothing), and done before the launch after that
+      // (whose predecessor's segment waits for it)
+      c->mirror_gen = c->mirror_gen == 0xFFFFFFFFu ? 2u : c->mirror_gen + 1;
+      kp.lufs_mirror = c->d_mirror + (c->mirror_gen & 1) * mir_n;
+      kp.mirror_gen = c->mirror_gen;
+      p.lufs_mirror = kp.lufs_mirror;
+      p.mirror_gen = c->mirror_gen;
+    } else {
+      kp.kw_done = c->d_kw_done;
+      c->kw_issued += (unsigned)n;
+      p.wait_ctr = c->d_kw_done;
+      p.wait_target = c->kw_issued;
+    }
+    if (fold)
+      if (int e = tail_init(c)) return e;
+    const bool tail = fold && c->tail_ok > 0;
+    if (tail) bp.tail_ctr = c->d_tail;
+    // unpipelined: the prep before the batch (it must be resident while the batch runs: its segment
+    // waits for it); pipelined: after it, behind the stream wait -- enqueued before the batch, a wait
+    // whose stream shared a hardware queue with the batch's would block the batch behind it for ever
+    if (!fold) HIPC(c, launch_meter_prep(p, c->fork[0]));
+    c->side_meters = true;
+    mq = mc[0];
+    mq.start_ctr = c->d_kw_done + 3;
+    mq.start_target = c->prep_issued + (unsigned)p.C;
+    // the meter segment's wait for the true peaks (each true-peak workgroup stores its value
+    // write-through and counts in); a pipelined segment runs in a later launch, after this batch ended
+    if (!fold) {
+      sp.tp_done = c->d_kw_done + 2;
+      mq.join_ctr = c->d_kw_done + 2;
+      mq.join_target = c->tp_issued + (unsigned)n;
+    }
+    const hipError_t le = launch_batch(sp, kp, bp, fold ? c->pend_mq : mq, (int)grid, s);
+    if (le != hipSuccess) {
+      // the prep kernel already waits for this batch's count: publish it (see below)
+      if (!fold) {
+        (void)hipMemcpy(c->d_kw_done, &c->kw_issued, sizeof(unsigned), hipMemcpyHostToDevice);
+        c->prep_issued += (unsigned)p.C;
+      } else {
+        // (no prep waits for this launch: nothing was enqueued; the generation goes back so the next
+        // launch takes the other parity)
+        c->mirror_gen = gen_was;
+        c->seg_par[a ^ 1] = seg_par_was;  // (the pending segment stays pending)
+        c->cur = cur_was;                 // (no prep writes the other parity's state)
+      }
+      return fail(c, OMEGA_EHIP, "batch launch: %s", hipGetErrorString(le));
+    }
+    if (!fold) c->tp_issued += (unsigned)n;
+    if (tail) {
+      HIPC(c, hipStreamWaitValue32(c->fork[0], c->d_tail, c->tail_issued + 1, hipStreamWaitValueGte, 0xFFFFFFFFu));
+      ++c->tail_issued;
+    }
+    if (fold) HIPC(c, launch_meter_prep(p, c->fork[0]));
+    c->side_meters = true;
+    c->prep_issued += (unsigned)p.C;
+    if (fold) {
+      if (c->pend) c->seg_issued += (unsigned)c->pend_nq;
+      c->pend = true;
+      c->pend_mq = mq;
+      c->pend_nq = (int)n_mq;
+      c->pend_par = a;
+    } else {
+      c->seg_par[a] = c->seg_issued + (unsigned)n_mq;
+      c->seg_issued += (unsigned)n_mq;
+    }
+    return 0;
+  }
+  if (meters) {
+    mc = meter_chunks(c, lufs, tp, n_frames, meters);
+    kp.kw_done = c->d_kw_done;
+    c->kw_issued += (unsigned)n;
+    for (size_t i = 0; i < mc.size(); ++i) {
+      MeterPrepParams p = mc[i];
+      if (i == 0) {
+        p.wait_ctr = c->d_kw_done;
+        p.wait_target = c->kw_issued;
+      }
+      HIPC(c, launch_meter_prep(p, c->fork[0]));
+      c->side_meters = true;
+      p.parts = 1;
+      p.q_done = c->d_kw_done + 1;
+      HIPC(c, launch_meter_query(p, c->fork[0]));
+      c->side_meters = true;
+      c->q_issued += (unsigned)(((p.n_frames + 3) / 4) * p.C);  // (counted once it is enqueued)
+    }
+  }
+  if (grid > 0) {
+    const hipError_t le = launch_batch(sp, kp, bp, mq, (int)grid, s);
+    if (le != hipSuccess) {
+      // the prep kernel already waits for this batch's count: publish it, so that it (and every later
+      // call's target) stays in step with the device counter instead of timing out
+      if (meters) (void)hipMemcpy(c->d_kw_done, &c->kw_issued, sizeof(unsigned), hipMemcpyHostToDevice);
+      return fail(c, OMEGA_EHIP, "batch launch: %s", hipGetErrorString(le));
+    }
+  }
+  for (size_t i = 0; i < mc.size(); ++i) {
+    MeterPrepParams p = mc[i];
+    p.parts = 2;
+    if (i + 1 == mc.size()) {
+      p.join_ctr = c->d_kw_done + 1;
+      p.join_target = c->q_issued;
+    }
+    HIPC(c, launch_meter_query(p, s));
+  }
+  return 0;
+}
+
+// The per-batch work: layout 3 (enqueue_batch) where eligible, otherwise the full-chip kernels back to
+// back on `s` (K-weighting first); the meter aggregates' prep and LUFS query kernels (one or two
+// workgroups per channel: latency-bound) run on fork[0] beside the resolution and true-peak kernels,
+// the true-peak meter after the true peaks on `s`. (Concurrent full-chip kernels lose to this: 512
+// channel-frames are exactly two rounds of 256 CUs, and a CU held by another kernel pushes a third.)
+// lufs_st / tp_st: the context's staging slots of a pipelined call with meters (omega_process_frames).
+int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int64_t n_frames, const float* lufs,
+                   const float* tp, double* meters, hipStream_t s, bool pipe = false, float* lufs_st = nullptr,
+                   float* tp_st = nullptr, bool serial = false) {
+  const bool do_tp = sp.tp_out != nullptr, do_kw = kp.lufs_out || kp.weighted_out;
+  const bool do_res = sp.comb_out != nullptr || sp.res[0].mag_out || sp.res[1].mag_out || sp.res[2].mag_out ||
+                      sp.res[3].mag_out;
+  int mr = -1;
+  const bool batch = c->layout == 3 && batch_eligible(c, sp, kp, W, do_res, s, &mr);
+  // a pending meter segment goes first: folded into this batch's launch when it has an in-grid meter
+  // segment of its own, else on its own
+  const bool fold = pipe && batch && meters && do_tp && do_kw && n_frames > 0 && n_frames <= kChunkFrames;
+  // overlapped (omega_ctx::bs): the batch and, behind it, its own meter segment on a batch stream
+  if (fold && c->bs[0])
+    if (int e = tail_init(c)) return e;
+  const bool ovl = fold && c->bs[0] && c->tail_ok > 0;
+  if ((c->pend && (!fold || ovl)) || (c->unjoined && !ovl))
+    if (int e = flush_meters(c)) return e;
+  if (fold && lufs_st && tp_st) {
+    // the segment and the prep read the staging slots; the caller's buffers get copies
+    if (kp.lufs_out != lufs_st) kp.lufs_copy = kp.lufs_out;
+    if (sp.tp_out != tp_st) sp.tp_copy = sp.tp_out;
+    kp.lufs_out = lufs_st;
+    sp.tp_out = tp_st;
+    lufs = lufs_st;
+    tp = tp_st;
+  }
+  if (ovl) {
+    const int k = (int)(c->bs_idx & 1);
+    hipStream_t b = c->bs[k];
+    // serial: this call touches memory the unjoined call reads or writes -- that one first
+    if (serial)
+      if (int e = join_batches(c)) return e;
+    // the input dependency: what the caller enqueued so far, before anything of this call
+    HIPC(c, hipEventRecord(c->ev_in, s));
+    HIPC(c, hipStreamWaitEvent(b, c->ev_in, 0));
+    // the gate: batch i starts placing workgroups once batch i - 1 has none left to place (its
+    // last-dispatched workgroup has bumped the tail count) and fills the slots its drain frees. The
+    // wait follows the launch it waits for (the previous call's): shared hardware queues serialise
+    if (c->tail_issued)
+      HIPC(c, hipStreamWaitValue32(b, c->d_tail, c->tail_issued, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    const int err = [&]() -> int {
+      if (int e = enqueue_batch(c, sp, kp, W, n_frames, lufs, tp, meters, b, mr, do_tp, do_kw, true)) return e;
+      // this call's meter segment, a launch of its own behind its batch: it polls the prep's count (the
+      // prep is enqueued: fork[0], behind the tail wait) and runs beside the next call's batch. Segments
+      // run in call order (each reads the true-peak history the one before rolled)
+      if (c->unjoined) HIPC(c, hipStreamWaitEvent(b, c->ev_done[k ^ 1], 0));
+      if (int e = flush_meters(c, b)) return e;
+      HIPC(c, hipEventRecord(c->ev_done[k], b));
+      // the deferred join: the caller's stream waits for the PREVIOUS call here, for this one in the
+      // next call (or a flush), so the next call's input dependency does not hold this batch's drain
+      if (c->unjoined) HIPC(c, hipStreamWaitEvent(s, c->ev_done[k ^ 1], 0));
+      return 0;
+    }();
+    if (err) {
+      // a step failed, possibly with the batch already on its stream: order whatever runs on both batch
+      // streams into the caller's stream now (a segment left pending is then launched there, behind
+      // its batch, by the next flush) and leave nothing unjoined
+      (void)hipEventRecord(c->ev_done[k], b);
+      if (c->unjoined) (void)hipStreamWaitEvent(s, c->ev_done[k ^ 1], 0);
+      (void)hipStreamWaitEvent(s, c->ev_done[k], 0);
+      c->unjoined = false;
+      c->prev_span.clear();
+      return err;
+    }
+    c->unjoined = true;
+    c->last_bs = k;
+    ++c->bs_idx;
+    return 0;
+  }
+  if (batch) return enqueue_batch(c, sp, kp, W, n_frames, lufs, tp, meters, s, mr, do_tp, do_kw, fold);
+  if (do_kw) HIPC(c, launch_kweight(W, kp, s));
+  std::vector<MeterPrepParams> mc;
+  if (meters) {
+    mc = meter_chunks(c, lufs, tp, n_frames, meters);
+    HIPC(c, hipEventRecord(c->ev_kw, s));
+    HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_kw, 0));
+    for (MeterPrepParams p : mc) {
+      HIPC(c, launch_meter_prep(p, c->fork[0]));
+      c->side_meters = true;
+      p.parts = 1;
+      HIPC(c, launch_meter_query(p, c->fork[0]));
+      c->side_meters = true;
+    }
+    HIPC(c, hipEventRecord(c->ev_join[0], c->fork[0]));
+  }
+  if (do_res) HIPC(c, c->res_independent ? launch_mrfft_independent(sp, s) : launch_mrfft(sp, s));
+  if (do_tp) HIPC(c, tp_launch(c, W, sp, s));
+  for (MeterPrepParams p : mc) {
+    p.parts = 2;
+    HIPC(c, launch_meter_query(p, s));
+  }
+  if (meters) HIPC(c, hipStreamWaitEvent(s, c->ev_join[0], 0));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+#ifdef OMEGA_STAMPS
+// Development build only (make dev): one kernel variant over n_cf channel-frames of the context's
+// frames x (device memory, frame stride W, channel stride W * ... as omega_process_frames with
+// frame_stride = C * W, channel_stride = W), outputs to device buffers. which: 0 the 16384-point
+// resolution kernel, 2 the true-peak kernel (aux: [n_cf] true peaks), 3 the same at one workgroup per
+// CU (dynamic LDS padded past half the CU's 160 KiB). (Two frames per workgroup
+// through one exchange buffer -- the 16384-point resolution interleaved, and a true peak with its
+// spectrum parked in L2 between phases -- measured no faster at 8192 channel-frames (true peak 614 vs
+// 621 us at a shader clock of 1773 vs 1897 MHz): the extra frames in flight bought activity and the
+// clock gave it back; both were deleted.)
+int omega_dev_probe(omega_ctx* c, int which, const float* x, int64_t n_frames, float* comb, float* aux) {
+  SpectralParams sp = spectral_params(c);
+  const int W = c->cfg.frame_size;
+  sp.x = x;
+  sp.frame_stride = (int64_t)c->cfg.n_channels * W;
+  sp.chan_stride = W;
+  sp.n_cf = n_frames * c->cfg.n_channels;
+  sp.comb_out = comb;
+  (void)aux;
+  for (int r = 0; r < kMaxRes; ++r) sp.res[r].mag_out = nullptr;
+  hipError_t e = hipErrorInvalidValue;
+  sp.tp_out = aux;
+  float2* rot = nullptr;
+  if (int r = get_rot(c, W, &rot)) return r;
+  sp.rot = rot;
+  if (which == 0) e = launch_mrfft_rf(16384, sp, 0, c->stream);
+  if (which == 2) e = launch_truepeak_rf(16384, sp, c->stream);
+  // 3: the true-peak kernel at one workgroup per CU (extra dynamic LDS), the occupancy probe
+  if (which == 3) e = launch_truepeak_rf(16384, sp, c->stream, 16 * 1024);
+  return e == hipSuccess ? 0 : fail(c, OMEGA_EHIP, "probe %d: %s", which, hipGetErrorString(e));
+}
+#endif
+
+int omega_meter_reset(omega_ctx* c) try {
+  if (!c) return OMEGA_EINVAL;
+  if (int e = flush_meters(c)) return e;  // (the pending segment reads the state being reset)
+  // a meter prep on the side stream may still be writing the next state after its count-in
+  if (c->fork[0]) HIPC(c, hipStreamSynchronize(c->fork[0]));
+  const int C = c->cfg.n_channels;
+  for (int b = 0; b < 2; ++b) {
+    HIPC(c, hipMemsetAsync(c->d_nl[b], 0, C * sizeof(int), c->stream));
+    HIPC(c, hipMemsetAsync(c->d_nt[b], 0, C * sizeof(int), c->stream));
+    HIPC(c, hipMemsetAsync(c->d_ns[b], 0, C * sizeof(int), c->stream));
+    HIPC(c, hipMemsetAsync(c->d_t0[b], 0, C * sizeof(uint32_t), c->stream));
+  }
+  HIPC(c, hipStreamSynchronize(c->stream));
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_process_frames(omega_ctx* c, const float* x, int64_t n_frames, int64_t frame_stride, int64_t channel_stride,
+                         const omega_outputs* out, int mem) try {
+  if (!c || !out) return OMEGA_EINVAL;
+  if (!x || n_frames < 0) return fail(c, OMEGA_EINVAL, "null input or negative frame count");
+  if (int e = check_device_err(c)) return e;
+  if (n_frames == 0) return 0;
+  const int C = c->cfg.n_channels, W = c->cfg.frame_size, T = c->cfg.target_bins;
+  const int64_t ncf = n_frames * C;
+  if ((frame_stride & 1) || (channel_stride & 1))
+    return fail(c, OMEGA_EINVAL, "frame_stride and channel_stride must be even (8-byte aligned frames)");
+  if (ncf > 0x7FFFFFFF) return fail(c, OMEGA_EINVAL, "too many channel-frames");
+  HIPC(c, hipSetDevice(c->device));
+  // meter pipelining applies to direct device-memory calls; any other call runs a pending meter
+  // segment first (before its staging buffers are touched)
+  const bool pipe = c->pipe && mem == OMEGA_MEM_DEVICE && !c->use_graph;
+  if (!pipe)
+    if (int e = flush_meters(c)) return e;
+  SpectralParams sp = spectral_params(c);
+  sp.frame_stride = frame_stride;
+  sp.chan_stride = channel_stride;
+  sp.n_cf = ncf;
+  float* mags[kMaxRes] = {};
+  const size_t span = (size_t)((n_frames - 1) * frame_stride + (C - 1) * channel_stride + W);
+  // when every kernel of a host-memory call only stores its outputs, small ones go straight to page-locked
+  // memory: not with meters (the meter path's true peaks are re-read across workgroups) nor with combine
+  // targets owned by several resolutions (their o[t] += v reads back across kernels): device staging
+  if (mem == OMEGA_MEM_HOST) c->zc_ok = !out->meters && (!out->combined || c->res_independent);
+  HostCall h(c, mem);
+  const float* dx = h.in(x, span * sizeof(float));
+  float* comb = h.out(out->combined, ncf * T);
+  float* lufs = h.out(out->lufs_inst, ncf);
+  float* tp = h.out(out->true_peak_db, ncf);
+  double* meters = h.out(out->meters, ncf * 5);
+  float* weighted = h.out(out->weighted, ncf * W);
+  for (int r = 0; r < c->cfg.n_res; ++r) mags[r] = h.out(out->mag[r], ncf * (c->cfg.res[r].fft_size / 2 + 1));
+  if (h.err) return h.err;
+  if (mem != OMEGA_MEM_HOST && !aligned8(x)) return fail(c, OMEGA_EINVAL, "input must be 8-byte aligned");
+  int e = 0;
+  // meters need the instantaneous values even when the caller does not ask for them. Pipelined, the
+  // meter prep and the deferred meter segment read them during the next call, so they read the
+  // context's staging slots (two sets in turn) and never the caller's buffers, which the next call may
+  // overwrite (the usual preallocated outputs): enqueue_frames points the batch's K-weighting and
+  // true-peak roles at the slots and hands them the caller's buffers as copies.
+  const int sl = pipe ? 2 * c->stage_par : 0;
+  if (pipe && meters) c->stage_par ^= 1;
+  float* lufs_st = nullptr;
+  float* tp_st = nullptr;
+  if (meters && (pipe || !lufs)) {
+    e = stage_buf(c, 10 + sl, ncf * sizeof(float), reinterpret_cast<void**>(&lufs_st));
+    if (e) return e;
+    if (!lufs) lufs = lufs_st;
+  }
+  if (meters && (pipe || !tp)) {
+    e = stage_buf(c, 11 + sl, ncf * sizeof(float), reinterpret_cast<void**>(&tp_st));
+    if (e) return e;
+    if (!tp) tp = tp_st;
+  }
+  sp.x = dx;
+  sp.comb_out = comb;
+  sp.tp_out = tp;
+  for (int r = 0; r < c->cfg.n_res; ++r) sp.res[r].mag_out = mags[r];
+  BiquadTab* tabs = nullptr;
+  if (lufs || weighted) {
+    e = get_kw_tab(c, W, &tabs);
+    if (e) return e;
+  }
+  KWeightParams kp{dx, frame_stride, channel_stride, C, ncf, tabs, tabs ? tabs + 1 : nullptr, lufs, weighted, 0};
+  if (mem == OMEGA_MEM_DEVICE && c->use_graph) {
+    // replay a captured graph of this exact call (pointers, sizes, meter-state parity), capturing it on
+    // first use: removes the per-launch host cost and runs the three branches concurrently
+    const std::vector<uint64_t> key = {(uint64_t)dx, (uint64_t)n_frames, (uint64_t)frame_stride,
+                                       (uint64_t)channel_stride, (uint64_t)comb, (uint64_t)lufs, (uint64_t)tp,
+                                       (uint64_t)meters, (uint64_t)weighted, (uint64_t)mags[0], (uint64_t)mags[1],
+                                       (uint64_t)mags[2], (uint64_t)mags[3], (uint64_t)c->cur};
+    hipGraphExec_t exec = nullptr;
+    for (auto& g : c->graphs)
+      if (g.key == key) exec = g.exec;
+    if (!exec) {
+      if (c->graphs.size() >= 16) drop_graphs(c);
+      const int cur0 = c->cur;
+      if (!c->cap) HIPC(c, hipStreamCreateWithFlags(&c->cap, hipStreamNonBlocking));
+      HIPC(c, hipStreamBeginCapture(c->cap, hipStreamCaptureModeThreadLocal));
+      e = enqueue_frames(c, sp, kp, W, n_frames, lufs, tp, meters, c->cap);
+      hipGraph_t graph = nullptr;
+      const hipError_t ce = hipStreamEndCapture(c->cap, &graph);
+      if (e) return e;
+      if (ce != hipSuccess) return fail(c, OMEGA_EHIP, "graph capture: %s", hipGetErrorString(ce));
+      HIPC(c, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+      c->graphs.push_back({key, graph, exec});
+      c->cur = cur0;  // capture advanced the parity; the replay below advances it for real
+    }
+    HIPC(c, hipGraphLaunch(exec, c->stream));
+    if (meters) c->cur ^= (int)(((n_frames + kChunkFrames - 1) / kChunkFrames) & 1);
+    return 0;
+  }
+  // overlapped pipelined calls: what this call reads ([0]) and writes; one that touches what the call
+  // still on its batch stream writes, or writes what that one reads, waits for it (two overlapped
+  // launches never write the same bytes, and an output passed on as input is complete)
+  std::vector<std::pair<const char*, size_t>> span_now;
+  bool serial = false;
+  if (pipe) {
+    auto add = [&](const void* p, size_t bytes) {
+      if (p) span_now.emplace_back(static_cast<const char*>(p), bytes);
+    };
+    span_now.emplace_back(reinterpret_cast<const char*>(x), span * sizeof(float));
+    add(comb, (size_t)ncf * T * sizeof(float));
+    add(out->lufs_inst, (size_t)ncf * sizeof(float));
+    add(out->true_peak_db, (size_t)ncf * sizeof(float));
+    add(meters, (size_t)ncf * OMEGA_N_METERS * sizeof(double));
+    add(weighted, (size_t)ncf * W * sizeof(float));
+    for (int r = 0; r < c->cfg.n_res; ++r) add(mags[r], (size_t)ncf * (c->cfg.res[r].fft_size / 2 + 1) * sizeof(float));
+    if (c->unjoined)
+      for (size_t i = 0; i < span_now.size() && !serial; ++i)
+        for (size_t j = 0; j < c->prev_span.size() && !serial; ++j)
+          serial = (i || j) && span_now[i].first < c->prev_span[j].first + c->prev_span[j].second &&
+                   c->prev_span[j].first < span_now[i].first + span_now[i].second;
+  }
+  e = enqueue_frames(c, sp, kp, W, n_frames, lufs, tp, meters, c->stream, pipe, lufs_st, tp_st, serial);
+  if (e) {
+    if (pipe && meters) c->stage_par ^= 1;  // (a still-pending segment reads the slots of the other parity)
+    return e;
+  }
+  if (c->unjoined) c->prev_span.swap(span_now);
+  return h.finish();
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_flush_meters(omega_ctx* c) try {
+  if (!c) return OMEGA_EINVAL;
+  if (!c->pend && !c->unjoined) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  return flush_meters(c);
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_process_stream(omega_ctx* c, const float* x, int64_t n_samples, int32_t hop, int64_t channel_stride,
+                         const omega_outputs* out, int mem, int64_t* n_frames_out) try {
+  if (!c) return OMEGA_EINVAL;
+  if (n_frames_out) *n_frames_out = 0;
+  if (hop < 1 || n_samples < 0) return fail(c, OMEGA_EINVAL, "hop must be >= 1 and n_samples >= 0");
+  const int W = c->cfg.frame_size;
+  const int64_t nf = n_samples < W ? 0 : (n_samples - W) / hop + 1;
+  if (n_frames_out) *n_frames_out = nf;
+  return omega_process_frames(c, x, nf, hop, channel_stride, out, mem);
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_true_peak(omega_ctx* c, const float* x, int64_t n, int32_t m, float* out_db, int mem) try {
+  return omega_true_peak_os(c, x, n, m, 4, out_db, mem);
+} catch (...) {
+  return guard_fail(c);
+}
+
+// Plan of the any-length transform: radices (4s, then 2, 3, 5, 7, then the remaining primes) and the
+// tables e^{-2 pi i m / N}, e^{2 pi i m / (4N)} in float64 rounded to float32
+int get_any_plan(omega_ctx* c, int N, omega_ctx::AnyPlan** out) {
+  auto it = c->any_plans.find(N);
+  if (it == c->any_plans.end()) {
+    omega_ctx::AnyPlan pl;
+    pl.radix = fft_radices(N);
+    if ((int)pl.radix.size() > kAnyMaxStages) return fail(c, OMEGA_EUNSUP, "length %d: too many factors", N);
+    std::vector<float2> tw(N), rot(3 * (N / 2) + 1);
+    for (int m = 0; m < N; ++m) tw[m] = make_float2((float)std::cos(2 * kPi * m / N), (float)-std::sin(2 * kPi * m / N));
+    for (size_t m = 0; m < rot.size(); ++m)
+      rot[m] = make_float2((float)std::cos(2 * kPi * (double)m / (4.0 * N)), (float)std::sin(2 * kPi * (double)m / (4.0 * N)));
+    int e = upload(c, &pl.tw, tw);
+    if (!e) e = upload(c, &pl.rot, rot);
+    if (e) return e;
+    it = c->any_plans.emplace(N, std::move(pl)).first;
+  }
+  *out = &it->second;
+  return 0;
+}
+
+// launches the any-length kernel over n frames in slices whose global scratch (N > kAnyLdsMax) stays
+// within 64 MiB; p.x / outputs advanced per slice
+int run_any(omega_ctx* c, AnyFftParams p, int truepeak) {
+  omega_ctx::AnyPlan* pl = nullptr;
+  if (int e = get_any_plan(c, p.N, &pl)) return e;
+  p.n_stages = (int)pl->radix.size();
+  for (int s = 0; s < p.n_stages; ++s) p.radix[s] = pl->radix[s];
+  p.tw = pl->tw;
+  p.rot = pl->rot;
+  for (int ph = 0; ph < 4; ++ph) p.nyq_cos[ph] = (float)std::cos(kPi * ph / 4.0);
+  const int64_t n = p.n;
+  int64_t per = n;
+  if (p.N > kAnyLdsMax) {
+    per = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(8 << 20) / (3 * (int64_t)p.N)));
+    if (int e = grow(c, &c->d_any, &c->any_cap, per * 3 * p.N)) return e;
+    p.scratch = c->d_any;
+  }
+  const int nb = p.N / 2 + 1;
+  for (int64_t f0 = 0; f0 < n; f0 += per) {
+    AnyFftParams q = p;
+    q.x = p.x + f0 * p.frame_stride;
+    q.n = std::min(per, n - f0);
+    if (q.tp_out) q.tp_out = p.tp_out + f0;
+    if (q.mag) q.mag = p.mag + f0 * nb;
+    if (q.cplx) q.cplx = p.cplx + f0 * nb * 2;
+    HIPC(c, launch_any(q, truepeak, c->stream));
+  }
+  return 0;
+}
+
+int omega_true_peak_os(omega_ctx* c, const float* x, int64_t n, int32_t m, int32_t oversampling, float* out_db,
+                       int mem) try {
+  if (!c || !x || !out_db) return OMEGA_EINVAL;
+  if (oversampling != 1 && oversampling != 2 && oversampling != 4)
+    return fail(c, OMEGA_EUNSUP, "true peak: oversampling %d unsupported (1, 2, 4)", oversampling);
+  if (m < 1) return fail(c, OMEGA_EINVAL, "true peak: frame length %d", m);
+  if (n <= 0) return n == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
+  const bool any = !is_pow2_in(m, 512, 16384);
+  HIPC(c, hipSetDevice(c->device));
+  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
+  const float* dx = h.in(x, (size_t)n * m * sizeof(float));
+  float* dout = h.out(out_db, n, 3);
+  if (h.err) return h.err;
+  int e = 0;
+  if (any) {  // frames of other lengths (anyfft.hip)
+    AnyFftParams ap{};
+    ap.x = dx;
+    ap.frame_stride = m;
+    ap.n = n;
+    ap.N = m;
+    ap.phases = oversampling == 4 ? 0xE : (oversampling == 2 ? 0x4 : 0);
+    ap.tp_out = dout;
+    if ((e = run_any(c, ap, 1))) return e;
+    return h.finish();
+  }
+  SpectralParams sp = spectral_params(c);
+  sp.x = dx;
+  sp.C = 1;
+  sp.frame_stride = m;
+  sp.chan_stride = 0;
+  sp.n_cf = n;
+  sp.comb_out = nullptr;
+  for (int r = 0; r < kMaxRes; ++r) sp.res[r].mag_out = nullptr;
+  sp.n_res = 0;
+  sp.tp_out = dout;
+  float2* rot = nullptr;
+  e = get_rot(c, m, &rot);
+  if (e) return e;
+  sp.rot = rot;
+  sp.tp_phases = oversampling == 4 ? 0xE : (oversampling == 2 ? 0x4 : 0);
+  sp.tp_done = c->tp_count_to;  // (omega_calculate_lufs)
+  HIPC(c, tp_launch(c, m, sp, c->stream));
+  return h.finish();
+} catch (...) {
+  return guard_fail(c);
+}
+
+// the batch kernel's float32 K-weighting (kweight_kernel) on its own, for power-of-two frames
+int omega_k_weighting(omega_ctx* c, const float* x, int64_t n, int32_t m, float* weighted, float* lufs_inst,
+                      int mem) try {
+  if (!c || !x) return OMEGA_EINVAL;
+  if (!is_pow2_in(m, 512, 16384)) return fail(c, OMEGA_EUNSUP, "k-weighting: frame length %d unsupported", m);
+  if (n <= 0) return n == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
+  HIPC(c, hipSetDevice(c->device));
+  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
+  const float* dx = h.in(x, (size_t)n * m * sizeof(float));
+  float* dw = h.out(weighted, (size_t)n * m, 5);
+  float* dl = h.out(lufs_inst, n, 2);
+  if (h.err) return h.err;
+  int e = 0;
+  BiquadTab* tabs = nullptr;
+  if ((e = get_kw_tab(c, m, &tabs))) return e;
+  KWeightParams kp{dx, m, 0, 1, n, tabs, tabs + 1, dl, dw, OMEGA_WEIGHT_K};
+  HIPC(c, launch_kweight(m, kp, c->stream));
+  return h.finish();
+} catch (...) {
+  return guard_fail(c);
+}
+
+// The float64 filter cascade of a weighting mode for the context's sample rate
+// (professional_meters.py:48-72, :74-127): K = {butter(2, 38 Hz, high), iirfilter(2, 1500 Hz, high)}
+// blended 0.3; A = {butter(2, 20.598997, high), butter(1, 107.65265, high), butter(1, 737.86223, low),
+// butter(2, min(12194.217 / nyq, 0.99), low)} x 2.5; C = {butter(2, 20.598997, high), butter(2, 12194.217, low)}.
+W64Stage w64_stage(const BiquadCoef& q, int order) {
+  W64Stage s{};
+  s.b0 = q.b[0];
+  s.b1 = q.b[1];
+  s.b2 = q.b[2];
+  s.a1 = q.a[1];
+  s.a2 = q.a[2];
+  // scipy.signal.lfilter_zi: solve (I - companion(a).T) zi = b[1:] - a[1:] b[0]
+  const double B0 = s.b1 - s.a1 * s.b0, B1 = s.b2 - s.a2 * s.b0;
+  s.zi0 = (B0 + B1) / (1.0 + s.a1 + s.a2);
+  s.zi1 = B1 - s.a2 * s.zi0;
+  s.E = 3 * (order + 1);  // filtfilt's default padlen 3 max(len(a), len(b))
+  return s;
+}
+
+int get_w64_stages(omega_ctx* c, int mode, W64Stage** out) {
+  if (c->w64[mode]) {
+    *out = c->w64[mode];
+    return 0;
+  }
+  const double fs = c->cfg.sample_rate, nyq = fs / 2;
+  const double f1 = 20.598997, f2 = 107.65265, f3 = 737.86223, f4 = 12194.217;
+  const double f4c = std::min(f4 / nyq, 0.99) * nyq;
+  std::vector<W64Stage> t;
+  if (mode == OMEGA_WEIGHT_K)
+    t = {w64_stage(butter2(38.0, fs, true), 2), w64_stage(butter2(1500.0, fs, true), 2)};
+  else if (mode == OMEGA_WEIGHT_A)
+    t = {w64_stage(butter2(f1, fs, true), 2), w64_stage(butter1(f2, fs, true), 1),
+         w64_stage(butter1(f3, fs, false), 1), w64_stage(butter2(f4c, fs, false), 2)};
+  else
+    t = {w64_stage(butter2(f1, fs, true), 2), w64_stage(butter2(f4c, fs, false), 2)};
+  if (int e = upload(c, &c->w64[mode], t)) return e;
+  *out = c->w64[mode];
+  return 0;
+}
+
+int omega_weighting(omega_ctx* c, const float* x, int64_t n, int32_t m, int32_t mode, float* weighted,
+                    float* lufs_inst, int mem) try {
+  if (!c || !x) return OMEGA_EINVAL;
+  if (mode < OMEGA_WEIGHT_K || mode > OMEGA_WEIGHT_Z) return fail(c, OMEGA_EINVAL, "weighting mode %d", mode);
+  // scipy's filtfilt needs more samples than its padlen (9 for the first section of K, A and C)
+  if (m < 1 || (mode != OMEGA_WEIGHT_Z && m <= 9))
+    return fail(c, OMEGA_EINVAL, "weighting: the length of the input (%d) must be greater than padlen (9)", m);
+  if (n <= 0) return n == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
+  HIPC(c, hipSetDevice(c->device));
+  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
+  const float* dx = h.in(x, (size_t)n * m * sizeof(float));
+  float* dw = h.out(weighted, (size_t)n * m, 5);
+  float* dl = h.out(lufs_inst, n, 2);
+  if (h.err) return h.err;
+  int e = 0;
+  Weight64Params p{};
+  p.M = m;
+  p.mode = mode;
+  if (mode != OMEGA_WEIGHT_Z) {
+    if ((e = get_w64_stages(c, mode, &p.st))) return e;
+    p.n_st = mode == OMEGA_WEIGHT_A ? 4 : 2;
+  }
+  // float64 working buffers per frame: the signal and its odd extension (at most 64 MiB per launch)
+  p.scratch_stride = 2 * (int64_t)m + 32;
+  const int64_t per_launch = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(8 << 20) / p.scratch_stride));
+  if ((e = grow(c, &c->d_w64, &c->w64_cap, per_launch * p.scratch_stride))) return e;
+  p.scratch = c->d_w64;
+  for (int64_t f0 = 0; f0 < n; f0 += per_launch) {
+    p.x = dx + f0 * m;
+    p.n = std::min(per_launch, n - f0);
+    p.weighted_out = dw ? dw + f0 * m : nullptr;
+    p.lufs_out = dl ? dl + f0 : nullptr;
+    HIPC(c, launch_weight64(p, c->stream));
+  }
+  return h.finish();
+} catch (...) {
+  return guard_fail(c);
+}
+
+// The meter aggregates on the caller's stream from device inputs. join_side: these kernels read the
+// state a meter prep on the side stream may still be writing (after its count-in), so the caller's
+// stream first waits for the side stream (a caller that has just joined it skips the second wait);
+// order_side: the next batch's meter prep runs on the side stream and reads, before its K-weighting
+// count, the state these kernels write, so the side stream is ordered after them (a host-memory
+// caller does it after its copies back, which then follow the kernels without an event between).
+int meter_update_dev(omega_ctx* c, const float* dl, const float* dt, int64_t n_frames, double* dm, bool join_side,
+                     bool order_side, unsigned* wait_ctr = nullptr, unsigned wait_target = 0) {
+  if (join_side) {
+    HIPC(c, hipEventRecord(c->ev_join[1], c->fork[0]));
+    HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[1], 0));
+  }
+  if (int e = meters_enqueue(c, dl, dt, n_frames, dm, c->stream, nullptr, wait_ctr, wait_target)) return e;
+  if (order_side) {
+    HIPC(c, hipEventRecord(c->ev_fork, c->stream));
+    HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_fork, 0));
+  }
+  return 0;
+}
+
+int omega_meter_update(omega_ctx* c, const float* lufs_inst, const float* tp_db, int64_t n_frames, double* meters,
+                       int mem) try {
+  if (!c || !lufs_inst || !tp_db || !meters) return OMEGA_EINVAL;
+  if (n_frames <= 0) return n_frames == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
+  if (int e = check_device_err(c)) return e;
+  HIPC(c, hipSetDevice(c->device));
+  if (int e = flush_meters(c)) return e;
+  const int64_t ncf = n_frames * c->cfg.n_channels;
+  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
+  const float* dl = h.in(lufs_inst, ncf * sizeof(float), 2);
+  const float* dt = h.in(tp_db, ncf * sizeof(float));
+  double* dm = h.out(meters, ncf * 5);
+  if (h.err) return h.err;
+  if (int e = meter_update_dev(c, dl, dt, n_frames, dm, true, true)) return e;
+  return h.finish();
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_meter_load_history(omega_ctx* c, const float* lufs_inst, int64_t n_l, const float* tp_db, int64_t n_t,
+                             int mem) try {
+  if (!c) return OMEGA_EINVAL;
+  if (n_l < 0 || n_t < 0 || n_t > n_l) return fail(c, OMEGA_EINVAL, "need 0 <= n_t <= n_l");
+  if ((n_l && !lufs_inst) || (n_t && !tp_db)) return fail(c, OMEGA_EINVAL, "null history");
+  // rows older than the windows hold (integrated_len - 1 LUFS values, peak_len - 1 true peaks) leave no
+  // trace in the state a replay of them would build: keep the last ones (a time-shard exchange hands over
+  // up to 3599 / 59 rows whatever this context's window lengths are)
+  if (n_l > c->HL) {
+    lufs_inst += (n_l - c->HL) * (int64_t)c->cfg.n_channels;
+    n_l = c->HL;
+  }
+  if (n_t > std::min<int64_t>(c->HT, n_l)) {
+    const int64_t k = std::min<int64_t>(c->HT, n_l);
+    tp_db += (n_t - k) * (int64_t)c->cfg.n_channels;
+    n_t = k;
+  }
+  if (int e = check_device_err(c)) return e;
+  HIPC(c, hipSetDevice(c->device));
+  if (int e = flush_meters(c)) return e;  // (a pending segment reads the state being replaced)
+  const int C = c->cfg.n_channels;
+  const float* dl = lufs_inst;
+  const float* dt = tp_db;
+  if (mem == OMEGA_MEM_HOST) {  // (raw staging: a null history of no rows still gets its slot's pointer)
+    int e = stage_in(c, 2, lufs_inst, (size_t)n_l * C * sizeof(float), reinterpret_cast<const void**>(&dl));
+    if (!e) e = stage_in(c, 3, tp_db, (size_t)n_t * C * sizeof(float), reinterpret_cast<const void**>(&dt));
+    if (e) return e;
+  }
+  // as omega_meter_update: after the side stream's last writes of the state, and before its next reads
+  HIPC(c, hipEventRecord(c->ev_join[1], c->fork[0]));
+  HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[1], 0));
+  const int a = c->cur;
+  MeterLoadParams p{dl, dt, (int)n_l, (int)n_t, C, c->HL, c->HT, (float)c->cfg.gate_lufs, c->d_hist_l[a],
+                    c->d_hist_t[a], c->d_nl[a], c->d_nt[a], c->d_skeys[a], c->d_ns[a], c->d_t0[a]};
+  HIPC(c, launch_meter_load(p, c->stream));
+  HIPC(c, hipEventRecord(c->ev_fork, c->stream));
+  HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_fork, 0));
+  if (mem == OMEGA_MEM_HOST) HIPC(c, hipStreamSynchronize(c->stream));
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_calculate_lufs(omega_ctx* c, const float* x, int64_t n_frames, int32_t m, int32_t mode, int32_t oversampling,
+                         float* lufs_inst, float* tp_db, double* meters, int mem) try {
+  if (!c || !x || !meters) return OMEGA_EINVAL;
+  if (n_frames <= 0) return n_frames == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
+  if (int e = check_device_err(c)) return e;
+  HIPC(c, hipSetDevice(c->device));
+  const int64_t ncf = n_frames * c->cfg.n_channels;
+  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
+  const float* dx = h.in(x, (size_t)ncf * m * sizeof(float));
+  float* dl = h.out(lufs_inst, ncf, 2);
+  float* dt = h.out(tp_db, ncf);
+  double* dm = h.out(meters, ncf * 5);
+  if (h.err) return h.err;
+  int e = 0;
+  // device scratch for the instantaneous values the caller does not want back
+  if (!dl || !dt) {
+    if ((e = grow(c, &c->d_lufs_scr, &c->lufs_scr_cap, 2 * ncf))) return e;
+    if (!dl) dl = c->d_lufs_scr;
+    if (!dt) dt = c->d_lufs_scr + ncf;
+  }
+  // The weighting and the true peak read the same input and write different outputs: the true peak
+  // runs on the side stream beside the weighting's latency-bound float64 scans (per-call metering of
+  // the app's 2048-sample frames: 37 + 14 us of kernels in sequence before). The aggregates read the
+  // meter state, which a meter prep on the side stream may still be writing, and the true peaks.
+  // Joining the side stream by an event costs ~5-10 us of idle GPU between kernels, so: when no meter
+  // kernel went to the side stream since the last join (the app's steady state: nothing but these
+  // calls; side_meters) there is nothing to join before, and the true peaks (power-of-two frames,
+  // direct launches) count themselves in on a device counter that the first meter prep polls before it
+  // reads them; otherwise events, as omega_meter_update.
+  const bool capture = c->cap && c->stream == c->cap;
+  const bool counted = !capture && is_pow2_in(m, 512, 16384);
+  if (counted && c->side_meters) {
+    HIPC(c, hipEventRecord(c->ev_join[1], c->fork[0]));
+    HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[1], 0));
+  }
+  c->side_meters = false;
+  HIPC(c, hipEventRecord(c->ev_fork, c->stream));
+  HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_fork, 0));
+  {
+    const hipStream_t main = c->stream;
+    c->stream = c->fork[0];
+    c->tp_count_to = counted ? c->d_kw_done + 5 : nullptr;
+    e = omega_true_peak_os(c, dx, ncf, m, oversampling, dt, OMEGA_MEM_DEVICE);
+    c->tp_count_to = nullptr;
+    c->stream = main;
+    if (e) return e;
+  }
+  if (counted) c->lt_issued += (unsigned)ncf;
+  if ((e = omega_weighting(c, dx, ncf, m, mode, nullptr, dl, OMEGA_MEM_DEVICE))) return e;
+  if (!counted) {
+    // the side stream's last work is the true peak, behind any earlier meter prep: one join serves
+    // both (omega_meter_update's second wait is skipped)
+    HIPC(c, hipEventRecord(c->ev_join[0], c->fork[0]));
+    HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[0], 0));
+  }
+  if ((e = flush_meters(c))) return e;
+  // for a host-memory call the side stream is ordered after the copies back (no event between the
+  // aggregates and the copies)
+  const bool host = mem == OMEGA_MEM_HOST;
+  if ((e = meter_update_dev(c, dl, dt, n_frames, dm, false, !host, counted ? c->d_kw_done + 5 : nullptr,
+                            c->lt_issued)))
+    return e;
+  if (host) {
+    if ((e = h.finish())) return e;
+    HIPC(c, hipEventRecord(c->ev_fork, c->stream));
+    HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_fork, 0));
+    return 0;
+  }
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+}  // extern "C"

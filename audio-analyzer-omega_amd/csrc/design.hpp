@@ -1,0 +1,39 @@
+// Pure host maths of the C API's tables (no HIP call): numpy's windows, np.fft.rfftfreq, scipy's
+// Butterworth designs and their state-space tables, Savitzky-Golay weights, numpy's pairwise-sum leaves.
+// Private to libomega.so: everything here is hidden from the dynamic symbol table.
+#pragma once
+
+#include <vector>
+
+#include "params.hpp"
+
+namespace omega_host __attribute__((visibility("hidden"))) {
+
+constexpr double kPi = 3.14159265358979323846;
+
+inline bool is_pow2_in(int v, int lo, int hi) { return v >= lo && v <= hi && (v & (v - 1)) == 0; }
+
+// Point i of np.blackman / np.hanning / np.hamming (M) in float64 (kind: OMEGA_WIN_*, any other 1.0);
+// M >= 2 (numpy returns ones(1) for M = 1: make_window's case)
+double np_window(int kind, int M, int i);
+std::vector<float> make_window(int M, int kind);
+
+double rfreq(int k, int N, double fs);
+
+struct BiquadCoef {
+  double b[3], a[3];
+};
+BiquadCoef butter2(double fc, double fs, bool high);
+BiquadCoef butter1(double fc, double fs, bool high);
+void butter4_highpass_sos(double fc, double fs, BiquadCoef out[2]);
+void butter4_bandpass_sos(double lo, double hi, double fs, double out[4][6]);
+
+void mat2_mul(const double* A, const double* B, double* C);
+omega::BiquadTab make_biquad_tab(const BiquadCoef& c, int L);
+
+// the mixed-radix transforms' stages for length n: 4s, then 2, 3, 5, 7, then the remaining primes
+std::vector<int> fft_radices(int n);
+void savgol_21_3(double W[21][21]);
+void np_leaves(int off, int n, int depth, std::vector<unsigned>& out);
+
+}  // namespace omega_host

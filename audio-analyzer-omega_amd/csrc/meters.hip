@@ -157,7 +157,7 @@ __global__ __launch_bounds__(1024) void meter_load_kernel(MeterLoadParams p) {
   }
 }
 
-// Side-stream concurrency probe (capi.cpp side_stream_check): the waiter, launched first on the side
+// Side-stream concurrency probe (capi_core.cpp side_stream_check): the waiter, launched first on the side
 // stream, polls (bounded) for the value the setter, launched after it on the context's stream, stores.
 // It sees it only when the two streams run on different hardware queues -- on a shared queue the setter
 // waits behind it. w[1] = target when seen, else 0.

@@ -70,7 +70,7 @@ __device__ __forceinline__ float np_mean_f32(const float* a, int n) {
 // interleaved accumulators (lane j: a[j] + a[j+8] + ..., in numpy's order), combined across the lanes in
 // numpy's tree ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the tail added by the leaf's first lane; lane 0
 // then adds the leaf sums in the recursion's order (np_leaf_combine). The leaves come from a host table
-// (capi.cpp np_leaves): tab[0] the count (<= 31), tab[1 ..] offset | length << 16.
+// (design.cpp np_leaves): tab[0] the count (<= 31), tab[1 ..] offset | length << 16.
 template <int D>
 __device__ __forceinline__ float np_leaf_combine(int n, const float* ls, int& idx) {
   if constexpr (D == 0) {

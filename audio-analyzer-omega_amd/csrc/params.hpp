@@ -1,4 +1,4 @@
-// Kernel parameter blocks shared by the host launcher (capi.cpp) and the device code.
+// Kernel parameter blocks shared by the host launcher (capi_*.cpp) and the device code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -275,7 +275,7 @@ struct BatchPlan {
   int mr_res;
   MultiPlan multi;
   int q_begin, q_n;
-  unsigned* tail_ctr;  // (meter pipelining) the last workgroup adds 1 at its start: see capi.cpp d_tail
+  unsigned* tail_ctr;  // (meter pipelining) the last workgroup adds 1 at its start: see host.hpp omega_ctx::d_tail
   int pat;
   int seg_start[2];
   int multi_start, multi_n;

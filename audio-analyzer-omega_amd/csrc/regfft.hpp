@@ -113,7 +113,7 @@ __device__ __forceinline__ void lane_pair_fmac(float2 (&v)[16], float s) {
 // register-FFT loads, where thread t takes the point pairs 2 (t + NTH q) + {0, 1}, q < 16: with
 // C_i = cos(2 pi i / (M - 1)) the window is w_i = c0 + C_i (c1 + c2 C_i), and C at the thread's points
 // is one rotation of its two base angles 2 pi (2t + e) / (M - 1) by the step 2 pi (2 NTH q) / (M - 1).
-// Table g (capi.cpp get_wingen): g[0] = {c0, c1, c2, -}, g[1 + q / 2] the steps' (cos, sin) (.xy for even
+// Table g (capi_spectrum.cpp get_wingen): g[0] = {c0, c1, c2, -}, g[1 + q / 2] the steps' (cos, sin) (.xy for even
 // q, .zw for odd), g[9 + t] = {cos, sin} of the base angles for e = 0 and e = 1. Each value is within
 // ~2e-7 of the float32 window table (cos / sin rounded once each on the host, one product-difference and
 // one Horner step here) -- far inside the FFT's own float32 error -- and the frame loop reads one

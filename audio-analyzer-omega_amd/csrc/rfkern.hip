@@ -776,13 +776,13 @@ __device__ __forceinline__ void batch_kw_role(const KWeightParams& kp, int64_t c
 // 8 q + w + 8 nq, ... = (frame o / C, channel o % C). Unpipelined the segment is the grid's last: its
 // workgroups are dispatched after every other role of the batch, so their waits cannot hold back the
 // batch work they wait for (pipelined, the previous call's segment waits for nothing and is dispatched
-// after the true peaks, ahead of the small resolutions: capi.cpp enqueue_batch): first
+// after the true peaks, ahead of the small resolutions: capi_batch.cpp enqueue_batch): first
 // (bounded) until the meter prep kernel on the side stream has counted in (it has waited for the
 // batch's K-weighting count), then the LUFS meters; then until every true-peak workgroup has counted
 // in, then the true-peak meter and the roll of the true-peak history. The batch completes only
 // after both, so the caller's stream needs no join kernel and no stream event. nq is at most
 // kMeterWgs (the host's cap): the waiting workgroups must leave room for the prep kernel, which may be
-// dispatched after them and needs a CU with at most one batch workgroup resident (capi.cpp kMeterWgs).
+// dispatched after them and needs a CU with at most one batch workgroup resident (capi_batch.cpp kMeterWgs).
 __device__ __forceinline__ void batch_meter_role(const MeterPrepParams& mp, int q, int nq, int tid) {
   const int64_t n_out = mp.n_frames * mp.C, step = (int64_t)nq * (kBatchThreads / 64);
   const int64_t o0 = (int64_t)q * (kBatchThreads / 64) + (tid >> 6);
@@ -830,7 +830,7 @@ __device__ __forceinline__ void batch_body(const SpectralParams& sp, const KWeig
   const int b = blockIdx.x;
   OMEGA_WG_BEGIN();
   // meter pipelining: the grid's last workgroup (dispatched last) releases the side stream's wait before
-  // the meter prep (capi.cpp omega_ctx::d_tail)
+  // the meter prep (host.hpp omega_ctx::d_tail)
   if (bp.tail_ctr && b == (int)gridDim.x - 1 && tid == 0)
     __hip_atomic_fetch_add(bp.tail_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (b >= bp.q_begin && b < bp.q_begin + bp.q_n) {

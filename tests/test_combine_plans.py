@@ -3,7 +3,7 @@
 Every implementation of the combine step (mrfft_frame's direct, pair-range and all-magnitudes variants,
 mrfft_rf_body's combine-only, parked-magnitudes and run_low paths, mrfft_small_kernel, mrfft_multi_kernel,
 the batch kernel's resolution roles and the stand-alone combine_kernel) applies one host-built CombEnt plan
-(capi.cpp build_spectral_tables). The plans below give targets 0 to 4 owners, end at Nyquist, start at
+(capi_core.cpp build_spectral_tables). The plans below give targets 0 to 4 owners, end at Nyquist, start at
 0 Hz, skip a resolution with a single in-range bin, leave most targets unowned, use 44.1 and 96 kHz weight
 tables and move target_bins to both sides of the direct / pair-range switch; the paths cover host and
 device memory, strided frames, magnitude outputs for all / one / no resolution, meters (the batch kernel

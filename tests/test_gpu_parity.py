@@ -784,7 +784,7 @@ def test_many_contexts_batch_meters():
     """Contexts created one after another in one process (each holds two streams; HIP deals streams out
     over 4 hardware queues per process): on every one of them the default batch path -- the batch kernel
     and the side stream's meter prep ordered by device counters, which needs the two on different queues
-    (capi.cpp side_stream_check) -- returns without OMEGA_EHIP and bitwise the outputs of the first context,
+    (capi_core.cpp side_stream_check) -- returns without OMEGA_EHIP and bitwise the outputs of the first context,
     through the context's own stream and through torch's stream."""
     import torch
     from omega_gpu import Engine, NORTHSTAR_RESOLUTIONS
@@ -808,7 +808,7 @@ def test_many_contexts_batch_meters():
 
 def test_side_stream_reprobed_with_busy_streams():
     """An RCCL-like neighbour: four more streams created after the context, each with a long-running
-    kernel in flight (torch.cuda._sleep), then omega_check_queues re-probes the pair (capi.cpp
+    kernel in flight (torch.cuda._sleep), then omega_check_queues re-probes the pair (capi_core.cpp
     side_stream_check) and in-call and pipelined batches with meters run beside them: no OMEGA_EHIP, and
     every output bitwise what the same sequence gives on a quiet context."""
     import torch
