@@ -52,6 +52,8 @@ hipError_t launch_harmonic(const HarmonicParams& p, hipStream_t s);
 hipError_t launch_genre(const GenreParams& p, hipStream_t s);
 hipError_t launch_hiphop(const HipHopParams& p, hipStream_t s);
 hipError_t launch_phase(const PhaseParams& p, hipStream_t s);
+hipError_t launch_room_modes(const RoomModesParams& p, hipStream_t s);
+hipError_t launch_room_rt60(const RoomRt60Params& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -127,6 +129,16 @@ struct PhaseState {
   bool set = false;
   PhaseParams p{};
   std::map<int, std::pair<double2*, double*>> tabs;
+};
+
+// capi_room.cpp -- room acoustics (omega_room_configure / omega_room_modes / omega_room_decay): the
+// configuration with the in-range bins and the uploaded frequency table (no frame state)
+struct RoomState {
+  bool set = false;
+  RoomModesParams p{};
+  double fs = 0.0;
+  double* freqs = nullptr;
+  int64_t freqs_cap = 0;
 };
 
 // capi_features.cpp -- the stream state of a feature that compares each frame's spectrum with the one
@@ -317,6 +329,7 @@ struct omega_ctx {
   GenreState genre;
   HipHopState hiphop;
   PhaseState phase;
+  RoomState room;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables

@@ -589,6 +589,40 @@ struct PhaseParams {
   double* points;           // [n_frames, kPhasePoints, 2] or nullptr
 };
 
+// RoomModeAnalyzer (room.hip; omega4/analyzers/room_modes.py:71-239 and :356-458): the room modes of a
+// batch of spectra, one workgroup per frame, and the Schroeder decay fit of a batch of sample histories, one
+// workgroup per stream
+constexpr int kRoomMaxModes = 64;
+constexpr int kRoomCols = 8;                   // see include/omega.h for the columns
+constexpr int kRoomRows = kRoomMaxModes + 1;   // the header row, then the modes
+constexpr int kRoomMaxBins = 4096;             // in-range bins held in LDS
+constexpr int kRoomThreads = 256;
+constexpr int kRt60Threads = 1024, kRt60Cols = 8;
+constexpr int kRt60MaxLen = 1 << 20;
+struct RoomModesParams {
+  const void* spec;         // frame f at spec + f * spec_stride, n_bins values
+  int64_t spec_stride;
+  int64_t n_frames;
+  int f64;                  // the spectra are float64 (else float32, widened on load)
+  int n_bins;
+  int first, last;          // the in-range bins [first, last) of the caller's table
+  int freqs_bad;            // the table holds a non-finite entry: every frame gets flag bit 0
+  const double* freqs;      // [n_bins] the caller's table
+  double height_mult, prom_std, min_q, max_q, min_sev;
+  double hints[6];          // axial fundamentals (length, width, height), tangential frequencies; [0] == 0: none
+  double* out;              // [n_frames, kRoomRows, kRoomCols]
+};
+struct RoomRt60Params {
+  const void* audio;        // stream s at audio + s * stream_stride, L samples
+  int64_t stream_stride;
+  int64_t n_streams;
+  int f64;
+  int L, W;                 // W > 0: frames of W samples (W divides L), their sums of squares to `energies`
+  double fs;
+  double* out;              // [n_streams, kRt60Cols]
+  double* energies;         // [n_streams, L / W] or nullptr
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

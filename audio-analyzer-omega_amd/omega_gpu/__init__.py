@@ -11,9 +11,11 @@ from .harmonic_analysis import HarmonicAnalyzer, HarmonicMetrics
 from .genre_classification import GenreClassifier
 from .hip_hop_detector import HipHopDetector
 from .phase_correlation import PhaseCorrelation
+from .room_modes import RoomModeAnalyzer, RoomModeConfig
 
 __all__ = [
     "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector", "PhaseCorrelation",
+    "RoomModeAnalyzer", "RoomModeConfig",
     "LIB_PATH", "OmegaError", "UnsupportedError", "lib", "Engine", "Resolution", "BandTable",
     "DEFAULT_RESOLUTIONS", "NORTHSTAR_RESOLUTIONS", "METER_KEYS",
     "CepstralAnalyzer", "PitchDetectionConfig", "get_preset_config", "list_presets",

@@ -71,6 +71,12 @@ class PhaseConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("m", C.c_int32)]
 
 
+class RoomConfig(C.Structure):
+    _fields_ = [(k, C.c_double) for k in (
+        "sample_rate", "min_frequency", "max_frequency", "peak_threshold_multiplier", "minimum_prominence_std",
+        "min_q_factor", "max_q_factor", "minimum_severity")]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -131,6 +137,12 @@ EXPORTS = {
     "omega_phase_configure": (C.c_int, [C.c_void_p, C.POINTER(PhaseConfig), C.c_void_p]),
     "omega_phase_correlation": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                           C.c_void_p, C.c_void_p, C.c_int]),
+    "omega_room_config_default": (None, [C.POINTER(RoomConfig)]),
+    "omega_room_bin_range": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p]),
+    "omega_room_configure": (C.c_int, [C.c_void_p, C.POINTER(RoomConfig), C.c_void_p, C.c_int32, C.c_void_p]),
+    "omega_room_modes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int]),
+    "omega_room_decay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                  C.c_void_p, C.c_void_p, C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -607,6 +607,67 @@ int omega_phase_configure(omega_ctx* ctx, const omega_phase_config* cfg, const d
 int omega_phase_correlation(omega_ctx* ctx, const void* left, const void* right, int32_t f64, int64_t frame_stride,
                             int64_t n_frames, double* out, double* points, int mem);
 
+/* RoomModeAnalyzer (omega4/analyzers/room_modes.py:71-239 detect_room_modes with estimate_q_factor and
+ * classify_room_mode; :356-458 the Schroeder and EDT decay estimates), all in float64 (float32 input is widened
+ * on load). The device keeps no state. The entry points are additive to ABI 5.
+ * omega_room_bin_range (no context, no device) applies the mask (freqs >= min_f) & (freqs <= max_f) to the
+ * caller's table (the app passes np.linspace(0, fs / 2, n), not rfftfreq; it is never recomputed here) and writes
+ * range[2] = [first, last); OMEGA_EINVAL unless freqs is strictly increasing.
+ * omega_room_configure stores the range and the thresholds and uploads the table; it must precede the two calls
+ * below and may be repeated. hints (may be NULL): the six frequencies classify_room_mode derives from the room
+ * dimension hints -- the axial fundamentals speed / (2 length), speed / (2 width), speed / (2 height), then the
+ * three tangential frequencies in the reference's order; NULL or any entry <= 0: no hints. More than
+ * OMEGA_ROOM_MAX_BINS bins in range return OMEGA_EUNSUP.
+ * omega_room_modes: n_frames spectra of n_bins values, frame f at spectra + f*spec_stride elements (rows may
+ * overlap). out [n_frames, OMEGA_ROOM_ROWS, OMEGA_ROOM_COLS] float64: row 0 is the header
+ *    0 count   the full number of modes          1 flags   bit 0: a non-finite bin in the whole spectrum or the
+ *    2 mean    np.mean of the in-range bins                table (no modes; other frames are unaffected);
+ *    3 std     np.std of them (two passes)                 bit 1: mean or std is 0, or no bin in range (no
+ *                                                          modes); bit 2: more than OMEGA_ROOM_MAX_MODES modes
+ * and rows 1.. are the first OMEGA_ROOM_MAX_MODES modes by severity descending, ties by ascending bin (Python's
+ * stable sorted(reverse=True)), zero past the count:
+ *    0 frequency  1 magnitude  2 q_factor  3 severity  4 type  5 prominence  6 bandwidth  7 bin (in the table)
+ * type = base + 8 harmonic; base 0 axial_length, 1 axial_width, 2 axial_height, 3 tangential, 4 oblique; harmonic
+ * 1..3 for the "_H<n>" types of a hinted room, else 0. The peak set is scipy's find_peaks(x, height = mean *
+ * peak_threshold_multiplier, prominence = std * minimum_prominence_std). frequency, magnitude, prominence,
+ * q_factor and bandwidth are the reference's IEEE operations on exact inputs, bit for bit; mean, std and
+ * severity agree to 1e-12 relative on frames with std >= 1e-3 mean (block sums stand for numpy's pairwise
+ * sums), and the peak set is the reference's where no height, prominence or severity decision lies within
+ * 1e-9 relative of its threshold.
+ * omega_room_decay: n_streams histories of L samples (2 <= L <= 2^20; longer: OMEGA_EUNSUP), stream s at
+ * audio + s*stream_stride elements. out [n_streams, OMEGA_ROOM_RT60_COLS] float64:
+ *    0 curve[0]   the sum of squares (before the 1e-10 floor)
+ *    1 idx5, 2 idx10, 3 idx35   the first index with 10 log10(curve / curve[0]) <= -5, -10, -35; L: none
+ *    4 slope, 5 intercept   of the least-squares line of the dB curve on i / sample_rate over [idx5, idx35)
+ *    6 r_squared  1 - SSR / SST of that line
+ *    7 flags      bit 0: a non-finite sample or square (the other columns are 0); bit 1: idx5 or idx35 is
+ *                 missing or idx35 <= idx5; bit 2: fewer than 3 points in [idx5, idx35); bit 3: slope >= 0.
+ *                 With bit 1 or 2 set columns 4-6 are 0.
+ * W > 0 (it must divide L) and energies [n_streams, L / W] non-NULL: also the sum of squares of every frame of
+ * W samples. slope, intercept and curve[0] agree with the reference called on float64 arrays to 1e-9 relative,
+ * r_squared to 1e-9 absolute, the indices exactly where the dB curve keeps 1e-9 dB from the thresholds. */
+#define OMEGA_ROOM_MAX_MODES 64
+#define OMEGA_ROOM_ROWS 65
+#define OMEGA_ROOM_COLS 8
+#define OMEGA_ROOM_MAX_BINS 4096
+#define OMEGA_ROOM_RT60_COLS 8
+typedef struct {
+  double sample_rate;
+  double min_frequency, max_frequency;
+  double peak_threshold_multiplier, minimum_prominence_std;
+  double min_q_factor, max_q_factor;
+  double minimum_severity;
+} omega_room_config;
+/* 48000 Hz and RoomModeConfig's defaults: 30..300 Hz, 2.0, 1.0, Q 0.5..100, severity 0.3. */
+void omega_room_config_default(omega_room_config* cfg);
+int omega_room_bin_range(const double* freqs, int32_t n_bins, double min_f, double max_f, int32_t* range);
+int omega_room_configure(omega_ctx* ctx, const omega_room_config* cfg, const double* freqs, int32_t n_bins,
+                         const double* hints);
+int omega_room_modes(omega_ctx* ctx, const void* spectra, int32_t f64, int64_t spec_stride, int64_t n_frames,
+                     double* out, int mem);
+int omega_room_decay(omega_ctx* ctx, const void* audio, int32_t f64, int64_t stream_stride, int64_t L, int64_t W,
+                    int64_t n_streams, double* out, double* energies, int mem);
+
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks
  * of chunk_size samples, s16 scaled by 1/32768), its per-chunk noise gate (:620-641: RMS, background

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Run one stage of the cfg2 hot path in isolation (for rocprofv3 counter passes and A/B timing).
 
-  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre} [--reps N]
+  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre,room} [--reps N]
 
 spectra-bands / spectra-chroma / spectra-mag: the cfg3 kernel with one output set only (where its LDS
 bank conflicts and time come from); spectra-rot: bench.py's cfg3 call, rotating over 4 distinct input
 batches (537 MB: the frames come from HBM, not the Infinity Cache).
+room: omega_room_modes over 512 resident spectra at K = 92 (16384-point) and K = 11 (2048-point) in-range bins
+and omega_room_decay over 8 resident histories of 122880 samples; one event pair per call, median / min / max.
 """
 import argparse
 import os
@@ -20,6 +22,53 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
+def room(reps):
+    """RoomModeAnalyzer's two device calls on resident inputs: per-call event times after warm-up."""
+    from omega_gpu import RoomModeAnalyzer
+    from omega_gpu import _lib as L
+    lib = L.lib()
+    rng = np.random.default_rng(12)
+
+    def timed(label, unit, n, call):
+        for _ in range(5):
+            call()
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(reps):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            call()
+            e.record()
+            e.synchronize()
+            us.append(s.elapsed_time(e) * 1e3)
+        med = float(np.median(us))
+        print(f"room {label}: median {med:.1f} us per call of {n} {unit} (min {min(us):.1f}, max {max(us):.1f}; "
+              f"{med / n:.3f} us per {unit[:-1]})")
+
+    t = np.arange(16384) / 48000.0
+    for m in (16384, 2048):
+        x = sum(np.sin(2 * np.pi * f * t[:m] + k) for k, f in enumerate((47.0, 94.0, 141.0, 230.0)))
+        x = x[None, :] + 0.02 * rng.standard_normal((512, m))
+        spec = torch.from_numpy(np.abs(np.fft.rfft(x * np.blackman(m), axis=1)).astype(np.float32)).cuda()
+        rm = RoomModeAnalyzer(48000)
+        freqs = np.linspace(0, 24000, m // 2 + 1)
+        rows = rm.analyze_spectra(spec, freqs)  # (configures the table)
+        K = int(np.sum((freqs >= 30) & (freqs <= 300)))
+        print(f"room modes K = {K}: {int(rows[0, 0, 0])} modes in frame 0")
+        rm._eng._bind_stream(spec)
+        timed(f"modes K = {K}", "frames", 512, lambda: rm._eng._check(lib.omega_room_modes(
+            rm._eng._ctx, spec.data_ptr(), 0, spec.shape[1], 512, rows.data_ptr(), L.MEM_DEVICE)))
+    Ln = 60 * 2048
+    h = rng.standard_normal((8, Ln)) * np.exp(-7.0 * np.arange(Ln) / Ln)[None, :]
+    for dt in (torch.float32, torch.float64):
+        hd = torch.from_numpy(h).to(dt).cuda()
+        out, en = rm.analyze_histories(hd, 2048)
+        timed(f"rt60 {str(dt).split('.')[1]}", "streams", 8, lambda: rm._eng._check(lib.omega_room_decay(
+            rm._eng._ctx, hd.data_ptr(), int(dt == torch.float64), Ln, Ln, 2048, 8, out.data_ptr(), en.data_ptr(),
+            L.MEM_DEVICE)))
+    print("room rt60 row 0:", out[0].cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("stage")
@@ -28,6 +77,8 @@ def main():
     ap.add_argument("--bins", type=int, default=512, help="genre: spectrum bins per frame (512, 4097)")
     ap.add_argument("--lib", default=None, help="another build in lib/ (A/B of two builds on one box)")
     a = ap.parse_args()
+    if a.stage == "room":
+        return room(a.reps)
     if a.lib:
         from omega_gpu import _lib as L0
         L0.use_development_library(a.lib)
