@@ -1,0 +1,127 @@
+// libomega.so host side: voice detection -- the voice-band energies, the formant peaks and the pitch
+// autocorrelation of a batch of frames (voice.hip).
+
+#include "host.hpp"
+
+namespace {
+
+// np.fft.rfftfreq(m, 1 / fs) as numpy evaluates it: val = 1.0 / (n * d), results = arange * val
+double rfftfreq_step(double fs, int m) {
+  const double d = 1.0 / fs;
+  return 1.0 / ((double)m * d);
+}
+
+// np.searchsorted(freq_bins, v) (side 'left') over the m / 2 + 1 bins
+int search_bins(double step, int n_freq, double v) {
+  int k = 0;
+  while (k < n_freq && (double)k * step < v) ++k;
+  return k;
+}
+
+bool voice_shape_ok(double fs, int m) {
+  return std::isfinite(fs) && fs >= kVoiceMinRate && is_pow2_in(m, kVoiceMinFrame, kVoiceMaxFrame);
+}
+
+}  // namespace
+
+extern "C" {
+
+void omega_voice_config_default(omega_voice_config* cfg) {
+  if (!cfg) return;
+  *cfg = omega_voice_config{};
+  cfg->sample_rate = 48000.0;
+  cfg->n_bins = 1025;
+  cfg->frame_len = 2048;
+}
+
+int omega_voice_bin_range(double sample_rate, int32_t frame_len, int32_t* range) try {
+  if (!range || !(sample_rate > 0.0) || !std::isfinite(sample_rate) || frame_len < 1) return OMEGA_EINVAL;
+  const double step = rfftfreq_step(sample_rate, frame_len);
+  range[0] = search_bins(step, frame_len / 2 + 1, 85.0);   // voice_detection.py:63-67
+  range[1] = search_bins(step, frame_len / 2 + 1, 255.0);
+  return 0;
+} catch (...) {
+  return guard_fail(nullptr);
+}
+
+int omega_voice_configure(omega_ctx* c, const omega_voice_config* cfg) try {
+  if (!c || !cfg) return OMEGA_EINVAL;
+  if (!(cfg->sample_rate > 0.0) || cfg->n_bins < 1 || cfg->frame_len < 1)
+    return fail(c, OMEGA_EINVAL, "voice: need a positive sample rate, bin count and frame length");
+  // (every size is refused before the configured table is touched)
+  if (cfg->n_bins > kVoiceMaxBins)
+    return fail(c, OMEGA_EUNSUP, "voice: %d spectrum bins (1..%d are built)", cfg->n_bins, kVoiceMaxBins);
+  if (!voice_shape_ok(cfg->sample_rate, cfg->frame_len))
+    return fail(c, OMEGA_EUNSUP, "voice: %d samples per frame at %g Hz (the powers of two %d..%d at %g Hz and above "
+                "are built)", cfg->frame_len, cfg->sample_rate, kVoiceMinFrame, kVoiceMaxFrame, kVoiceMinRate);
+  HIPC(c, hipSetDevice(c->device));
+  VoiceState& v = c->voice;
+  const int K = cfg->n_bins, m = cfg->frame_len;
+  const int w = K > 10 ? std::min(11, K / 4 * 2 + 1) : 0;  // :95-97
+  const double* sg = nullptr;
+  if (w) {
+    const int wi = (w - 5) / 2;
+    if (!v.sg[wi]) {
+      std::vector<double> W((size_t)w * w);
+      savgol_cubic(w, W.data());
+      if (int e = upload(c, &v.sg[wi], W)) return e;
+    }
+    sg = v.sg[wi];
+  }
+  VoiceParams p{};
+  p.n_bins = K;
+  p.m = m;
+  p.n_freq = m / 2 + 1;
+  p.bin_hz = rfftfreq_step(cfg->sample_rate, m);
+  p.voice_start = search_bins(p.bin_hz, p.n_freq, 85.0);
+  p.voice_end = search_bins(p.bin_hz, p.n_freq, 255.0);
+  p.sg_w = w;
+  p.sg = sg;
+  p.lag_lo = (int)std::min(cfg->sample_rate / 400.0, (double)m);  // :182-183 (Python's int() truncates)
+  const double hi = cfg->sample_rate / 80.0;
+  p.lag_hi = hi < (double)m ? (int)hi : m;
+  p.pitch = m >= kVoicePitchFrame && p.lag_hi < m;  // :174, :185
+  v.p = p;
+  v.set = true;
+  return 0;
+} catch (...) {
+  return guard_fail(c);
+}
+
+int omega_voice_features(omega_ctx* c, const float* spectra, int64_t spec_stride, const void* frames, int32_t f64,
+                         int32_t m, int64_t frame_stride, int64_t n_frames, double* out, int mem) try {
+  if (!c || !out) return OMEGA_EINVAL;
+  if (!c->voice.set) return fail(c, OMEGA_EINVAL, "voice: omega_voice_configure has not been called");
+  const VoiceParams& cp = c->voice.p;
+  if (!spectra || n_frames < 0 || spec_stride < 1) return fail(c, OMEGA_EINVAL, "voice: bad spectrum layout");
+  if (m != cp.m) return fail(c, OMEGA_EINVAL, "voice: %d samples per frame, configured for %d", m, cp.m);
+  // (a shape that gives no pitch never reads the audio)
+  if (cp.pitch && (!frames || frame_stride < 1)) return fail(c, OMEGA_EINVAL, "voice: bad audio layout");
+  if (n_frames == 0) return 0;
+  HIPC(c, hipSetDevice(c->device));
+  const size_t el = f64 ? 8 : 4;
+  HostCall h(c, mem);
+  const float* dspec = h.in(spectra, (size_t)((n_frames - 1) * spec_stride + cp.n_bins) * sizeof(float));
+  const void* daudio = cp.pitch ? h.in(frames, (size_t)((n_frames - 1) * frame_stride + m) * el) : nullptr;
+  double* dout = h.out(out, (size_t)n_frames * kVoiceCols);
+  if (h.err) return h.err;
+  // one launch covers at most 2^30 workgroups (two per frame)
+  if (int e = for_frame_chunks(n_frames, (int64_t)1 << 29, [&](int64_t f0, int64_t count) -> int {
+    VoiceParams q = cp;
+    q.f64 = f64 ? 1 : 0;
+    q.spec_stride = spec_stride;
+    q.audio_stride = frame_stride;
+    q.n_frames = count;
+    q.spec = dspec + f0 * spec_stride;
+    q.audio = daudio ? static_cast<const char*>(daudio) + (size_t)(f0 * frame_stride) * el : nullptr;
+    q.out = dout + f0 * kVoiceCols;
+    HIPC(c, launch_voice(q, c->stream));
+    return 0;
+  }))
+    return e;
+  return h.finish();
+} catch (...) {
+  return guard_fail(c);
+}
+
+}  // extern "C"

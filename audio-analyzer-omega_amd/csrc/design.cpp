@@ -240,6 +240,47 @@ void savgol_21_3(double W[21][21]) {
   }
 }
 
+// savgol_21_3 for any odd window w >= 5: W[p * w + t] is the weight of window sample t in the least-squares
+// cubic's value at window position p (p = w / 2: the interior correlation; the other rows: the 'interp' edges),
+// in the centred, scaled coordinate u = (t - h) / h, h = w / 2.
+void savgol_cubic(int w, double* W) {
+  const int h = w / 2;
+  std::vector<double> A((size_t)w * 4);
+  double G[4][4] = {};
+  for (int t = 0; t < w; ++t)
+    for (int j = 0; j < 4; ++j) A[(size_t)t * 4 + j] = std::pow((t - h) / (double)h, j);
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j)
+      for (int t = 0; t < w; ++t) G[i][j] += A[(size_t)t * 4 + i] * A[(size_t)t * 4 + j];
+  double M[4][8];  // Gauss-Jordan inverse of the normal matrix
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 8; ++j) M[i][j] = j < 4 ? G[i][j] : (j - 4 == i ? 1.0 : 0.0);
+  for (int c = 0; c < 4; ++c) {
+    int pv = c;
+    for (int r = c + 1; r < 4; ++r)
+      if (std::fabs(M[r][c]) > std::fabs(M[pv][c])) pv = r;
+    for (int j = 0; j < 8; ++j) std::swap(M[c][j], M[pv][j]);
+    const double d = M[c][c];
+    for (int j = 0; j < 8; ++j) M[c][j] /= d;
+    for (int r = 0; r < 4; ++r)
+      if (r != c) {
+        const double f = M[r][c];
+        for (int j = 0; j < 8; ++j) M[r][j] -= f * M[c][j];
+      }
+  }
+  for (int p = 0; p < w; ++p) {
+    double v[4], q[4] = {};
+    for (int j = 0; j < 4; ++j) v[j] = std::pow((p - h) / (double)h, j);
+    for (int j = 0; j < 4; ++j)
+      for (int i = 0; i < 4; ++i) q[j] += v[i] * M[i][j + 4];
+    for (int t = 0; t < w; ++t) {
+      double s = 0.0;
+      for (int j = 0; j < 4; ++j) s += q[j] * A[(size_t)t * 4 + j];
+      W[(size_t)p * w + t] = s;
+    }
+  }
+}
+
 // The leaves of numpy's pairwise float32 sum over n elements (numpy/_core/src/umath/loops_utils.h.src:
 // up to 128 elements a leaf, above that halves split at a multiple of 8 below n / 2), in the
 // recursion's depth-first order, as offset | length << 16 -- the table post_frame_kernel's range means

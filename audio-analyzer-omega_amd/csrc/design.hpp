@@ -34,6 +34,8 @@ omega::BiquadTab make_biquad_tab(const BiquadCoef& c, int L);
 // the mixed-radix transforms' stages for length n: 4s, then 2, 3, 5, 7, then the remaining primes
 std::vector<int> fft_radices(int n);
 void savgol_21_3(double W[21][21]);
+// the same for any odd window w >= 5 (cubic): W[p * w + t], p the output's position in the window
+void savgol_cubic(int w, double* W);
 void np_leaves(int off, int n, int depth, std::vector<unsigned>& out);
 
 }  // namespace omega_host

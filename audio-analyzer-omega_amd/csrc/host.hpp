@@ -54,6 +54,7 @@ hipError_t launch_hiphop(const HipHopParams& p, hipStream_t s);
 hipError_t launch_phase(const PhaseParams& p, hipStream_t s);
 hipError_t launch_room_modes(const RoomModesParams& p, hipStream_t s);
 hipError_t launch_room_rt60(const RoomRt60Params& p, hipStream_t s);
+hipError_t launch_voice(const VoiceParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -139,6 +140,14 @@ struct RoomState {
   double fs = 0.0;
   double* freqs = nullptr;
   int64_t freqs_cap = 0;
+};
+
+// capi_voice.cpp -- voice detection (omega_voice_configure / omega_voice_features): the configuration with the
+// voice bin range and the lag range (no frame state), and the Savitzky-Golay weights of the four windows
+struct VoiceState {
+  bool set = false;
+  VoiceParams p{};
+  double* sg[4] = {};  // windows 5, 7, 9, 11
 };
 
 // capi_features.cpp -- the stream state of a feature that compares each frame's spectrum with the one
@@ -330,6 +339,7 @@ struct omega_ctx {
   HipHopState hiphop;
   PhaseState phase;
   RoomState room;
+  VoiceState voice;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables

@@ -623,6 +623,35 @@ struct RoomRt60Params {
   double* energies;         // [n_streams, L / W] or nullptr
 };
 
+// VoiceDetectionPanel's per-frame analysis (voice.hip; omega4/panels/voice_detection.py:57-122 and :169-192):
+// two workgroups per frame in one launch, the spectrum side (blockIdx < n_frames) and, where a pitch can be
+// taken at all, the audio side
+constexpr int kVoiceCols = 17;       // see include/omega.h for the columns
+constexpr int kVoiceThreads = 256;
+constexpr int kVoiceMaxBins = 8193;
+constexpr int kVoiceMinFrame = 64, kVoiceMaxFrame = 8192;
+constexpr int kVoicePitchFrame = 2048;  // :174 shorter frames give no pitch
+constexpr double kVoiceMinRate = 8000.0;
+constexpr int kVoiceLagBlock = 4;    // lags per thread of the autocorrelation
+constexpr int kVoicePad = 8;         // zeros behind the staged audio frame (the lag block's overrun)
+struct VoiceParams {
+  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values
+  int64_t spec_stride;
+  const void* audio;        // frame f at audio + f * audio_stride, m samples (float32, or float64 when f64)
+  int64_t audio_stride;
+  int64_t n_frames;
+  int f64;
+  int n_bins, m;
+  int n_freq;               // m / 2 + 1: len(np.fft.rfftfreq(m, 1 / fs))
+  double bin_hz;            // rfftfreq's factor 1.0 / (m * (1 / fs)): freq_bins[k] = k * bin_hz
+  int voice_start, voice_end;  // searchsorted(freq_bins, 85), searchsorted(freq_bins, 255)
+  int sg_w;                 // savgol window min(11, n_bins / 4 * 2 + 1); 0: n_bins <= 10, no smoothing
+  const double* sg;         // [sg_w, sg_w] Savitzky-Golay (sg_w, 3) weights by output position in the window
+  int pitch;                // m >= 2048 and int(fs / 80) < m: the audio side runs
+  int lag_lo, lag_hi;       // int(fs / 400), int(fs / 80)
+  double* out;              // [n_frames, kVoiceCols]
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

@@ -77,6 +77,10 @@ class RoomConfig(C.Structure):
         "min_q_factor", "max_q_factor", "minimum_severity")]
 
 
+class VoiceConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_double), ("n_bins", C.c_int32), ("frame_len", C.c_int32)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -143,6 +147,11 @@ EXPORTS = {
     "omega_room_modes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int]),
     "omega_room_decay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                   C.c_void_p, C.c_void_p, C.c_int]),
+    "omega_voice_config_default": (None, [C.POINTER(VoiceConfig)]),
+    "omega_voice_bin_range": (C.c_int, [C.c_double, C.c_int32, C.c_void_p]),
+    "omega_voice_configure": (C.c_int, [C.c_void_p, C.POINTER(VoiceConfig)]),
+    "omega_voice_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                       C.c_int64, C.c_void_p, C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

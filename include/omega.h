@@ -668,6 +668,50 @@ int omega_room_modes(omega_ctx* ctx, const void* spectra, int32_t f64, int64_t s
 int omega_room_decay(omega_ctx* ctx, const void* audio, int32_t f64, int64_t stream_stride, int64_t L, int64_t W,
                     int64_t n_streams, double* out, double* energies, int mem);
 
+/* VoiceDetectionPanel (omega4/panels/voice_detection.py:57-122 detect_voice with _detect_formant_structure,
+ * :169-192 the autocorrelation of detect_pitch) for a batch of independent frames; the device keeps no state.
+ * The entry points are additive to ABI 5.
+ * omega_voice_bin_range (no context, no device): range[2] = [voice_start, voice_end] =
+ * np.searchsorted(freq_bins, 85), np.searchsorted(freq_bins, 255) over freq_bins = np.fft.rfftfreq(frame_len,
+ * 1 / sample_rate) as numpy evaluates it, arange * (1.0 / (frame_len * (1 / sample_rate))).
+ * omega_voice_configure fixes the shape and may be repeated. Built: n_bins 1..OMEGA_VOICE_MAX_BINS, frame_len a
+ * power of two 64..8192, sample_rate >= 8000; anything else returns OMEGA_EUNSUP and leaves the configured shape
+ * as it was.
+ * omega_voice_features: frame f has its spectrum (n_bins float32) at spectra + f*spec_stride and its m = frame_len
+ * samples (float32, or float64 when f64) at frames + f*frame_stride, both in elements; rows may overlap. The
+ * samples are read only where a pitch can be taken at all (frame_len >= 2048 and int(sample_rate / 80) <
+ * frame_len); otherwise frames may be NULL. out [n_frames, OMEGA_VOICE_COLS] float64:
+ *    0 flags         bit 0: the range check voice_start < n_bins and voice_end < n_bins failed (the reference
+ *                    leaves its state as it was); bit 1: total_energy <= 0; bit 2: a non-finite bin or sample
+ *                    (every other column is 0; other frames are unaffected); bit 3: no pitch for this shape
+ *    1 voice_start, 2 voice_end
+ *    3 voice_energy  sum(spectrum[voice_start:voice_end]), 4 total_energy  sum(spectrum): float64 sums of the
+ *                    float32 bins (0 with bit 0)
+ *    5 formant_count the ranges 200-900, 800-2500, 2000-3500, 3000-4500 Hz (ends included) that hold a peak
+ *    6..9 the bin and 10..13 freq_bins[bin] of each range's first peak, 0 where the range holds none (a peak is
+ *                    never bin 0). One peak may serve two ranges. All 0 with bit 0 or 1, or n_bins <= 10.
+ *    14 corr0        c[0] of c[l] = sum_n x[n] x[n + l] in float64
+ *    15 peak_lag     np.argmax over l in [int(sample_rate / 400), int(sample_rate / 80)), the first of equal maxima
+ *    16 corr_peak    c[peak_lag]; 14..16 are 0 with bit 3
+ * The peaks are those of scipy.signal.find_peaks(smoothed, prominence=np.max(smoothed) * 0.1) with smoothed =
+ * scipy.signal.savgol_filter(spectrum, min(11, n_bins // 4 * 2 + 1), 3) in float32; smoothed is within 1 ulp of
+ * scipy's, so the peak set is the reference's where no comparison of neighbouring smoothed values and no
+ * prominence lies that close to its decision. Frequencies are bit-equal to numpy's; the sums agree with a
+ * float64 evaluation to 1e-12 relative, corr0 and corr_peak to 1e-9 of corr0. */
+#define OMEGA_VOICE_COLS 17
+#define OMEGA_VOICE_MAX_BINS 8193
+typedef struct {
+  double sample_rate;
+  int32_t n_bins;     /* bins per spectrum (the app: 1025) */
+  int32_t frame_len;  /* samples per audio frame (the app: 2048) */
+} omega_voice_config;
+/* 48000 Hz, 1025 bins, 2048 samples. */
+void omega_voice_config_default(omega_voice_config* cfg);
+int omega_voice_bin_range(double sample_rate, int32_t frame_len, int32_t* range);
+int omega_voice_configure(omega_ctx* ctx, const omega_voice_config* cfg);
+int omega_voice_features(omega_ctx* ctx, const float* spectra, int64_t spec_stride, const void* frames, int32_t f64,
+                         int32_t m, int64_t frame_stride, int64_t n_frames, double* out, int mem);
+
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks
  * of chunk_size samples, s16 scaled by 1/32768), its per-chunk noise gate (:620-641: RMS, background

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Run one stage of the cfg2 hot path in isolation (for rocprofv3 counter passes and A/B timing).
 
-  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre,room} [--reps N]
+  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre,room,voice} [--reps N]
 
 spectra-bands / spectra-chroma / spectra-mag: the cfg3 kernel with one output set only (where its LDS
 bank conflicts and time come from); spectra-rot: bench.py's cfg3 call, rotating over 4 distinct input
 batches (537 MB: the frames come from HBM, not the Infinity Cache).
 room: omega_room_modes over 512 resident spectra at K = 92 (16384-point) and K = 11 (2048-point) in-range bins
 and omega_room_decay over 8 resident histories of 122880 samples; one event pair per call, median / min / max.
+voice: omega_voice_features over 512 resident frames at the app's shape (K 1025, m 2048, float64 audio): the
+golden's `app` frames (tests/golden/voice.npz) repeated.
 """
 import argparse
 import os
@@ -69,6 +71,38 @@ def room(reps):
     print("room rt60 row 0:", out[0].cpu().numpy())
 
 
+def voice(reps):
+    """VoiceDetectionPanel's device call on resident inputs: per-call event times after warm-up."""
+    from omega_gpu import VoiceDetectionPanel
+    from omega_gpu import _lib as L
+    lib = L.lib()
+    G = np.load(os.path.join(REPO, "tests", "golden", "voice.npz"))
+    fr = G["app/frame"].astype(np.float64) * np.hanning(2048)
+    pick = np.arange(512) % len(fr)
+    spec = torch.from_numpy(G["app/spec"][pick]).cuda()
+    audio = torch.from_numpy(fr[pick]).cuda()
+    vp = VoiceDetectionPanel(48000)
+    rows = vp.analyze_frames(spec, audio)  # (configures the shape)
+    print("voice row 0:", rows[0].cpu().numpy())
+    vp._eng._bind_stream(spec)
+    call = lambda: vp._eng._check(lib.omega_voice_features(  # noqa: E731
+        vp._eng._ctx, spec.data_ptr(), 1025, audio.data_ptr(), 1, 2048, 2048, 512, rows.data_ptr(), L.MEM_DEVICE))
+    for _ in range(5):
+        call()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(reps):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        call()
+        e.record()
+        e.synchronize()
+        us.append(s.elapsed_time(e) * 1e3)
+    med = float(np.median(us))
+    print(f"voice K = 1025, m = 2048: median {med:.1f} us per call of 512 frames (min {min(us):.1f}, max "
+          f"{max(us):.1f}; {med / 512:.3f} us per frame)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("stage")
@@ -79,6 +113,8 @@ def main():
     a = ap.parse_args()
     if a.stage == "room":
         return room(a.reps)
+    if a.stage == "voice":
+        return voice(a.reps)
     if a.lib:
         from omega_gpu import _lib as L0
         L0.use_development_library(a.lib)
