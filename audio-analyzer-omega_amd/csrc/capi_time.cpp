@@ -3,6 +3,30 @@
 
 #include "host.hpp"
 
+namespace omega_host {
+
+// the float64 tables of hilbert64.hpp's n-point real transform (n a power of two): e^{-2 pi i m / (n / 2)} for
+// m < n / 4 and e^{-2 pi i q / n} for q <= n / 2; kept per n in the transient state
+int tr_pow2_tables(omega_ctx* c, int n, const double2** tw, const double2** tw2) {
+  auto it = c->tr.tw.find(n);
+  if (it == c->tr.tw.end()) {
+    const int K = n / 2;
+    std::vector<double2> t1(K / 2 > 0 ? K / 2 : 1), t2(K + 1);
+    for (int m = 0; m < K / 2; ++m) t1[m] = make_double2(std::cos(2 * M_PI * m / K), -std::sin(2 * M_PI * m / K));
+    for (int q = 0; q <= K; ++q) t2[q] = make_double2(std::cos(2 * M_PI * q / n), -std::sin(2 * M_PI * q / n));
+    double2 *d1 = nullptr, *d2 = nullptr;
+    int e = upload(c, &d1, t1);
+    if (!e) e = upload(c, &d2, t2);
+    if (e) return e;
+    it = c->tr.tw.emplace(n, std::make_pair(d1, d2)).first;
+  }
+  *tw = it->second.first;
+  *tw2 = it->second.second;
+  return 0;
+}
+
+}  // namespace omega_host
+
 extern "C" {
 
 int omega_vu_reset(omega_ctx* c) try {
@@ -110,18 +134,9 @@ int omega_transients(omega_ctx* c, const void* x, int32_t f64, int64_t n_frames,
     if (int e = grow(c, &c->tr.scratch, &c->tr.scratch_cap, per * 2 * (int64_t)n)) return e;
     p.scratch = c->tr.scratch;
   }
-  auto it = c->tr.tw.find(pow2 ? n : 0);
-  if (pow2 && it == c->tr.tw.end()) {
-    const int K = n / 2;
-    std::vector<double2> t1(K / 2 > 0 ? K / 2 : 1), t2(K + 1);
-    for (int m = 0; m < K / 2; ++m) t1[m] = make_double2(std::cos(2 * M_PI * m / K), -std::sin(2 * M_PI * m / K));
-    for (int q = 0; q <= K; ++q) t2[q] = make_double2(std::cos(2 * M_PI * q / n), -std::sin(2 * M_PI * q / n));
-    double2 *d1 = nullptr, *d2 = nullptr;
-    int e = upload(c, &d1, t1);
-    if (!e) e = upload(c, &d2, t2);
-    if (e) return e;
-    it = c->tr.tw.emplace(n, std::make_pair(d1, d2)).first;
-  }
+  const double2 *tw = nullptr, *tw2 = nullptr;
+  if (pow2)
+    if (int e = tr_pow2_tables(c, n, &tw, &tw2)) return e;
   const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
   const void* dx = h.in(x, (size_t)((n_frames - 1) * frame_stride + n) * el);
@@ -136,8 +151,8 @@ int omega_transients(omega_ctx* c, const void* x, int32_t f64, int64_t n_frames,
     p.x = dx;
     p.n_frames = n_frames;
     p.out = dout;
-    p.tw = it->second.first;
-    p.tw2 = it->second.second;
+    p.tw = tw;
+    p.tw2 = tw2;
     HIPC(c, launch_transients(p, c->stream));
   } else {
     if (int e = for_frame_chunks(n_frames, per, [&](int64_t f0, int64_t count) -> int {

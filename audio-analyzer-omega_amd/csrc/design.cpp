@@ -135,6 +135,59 @@ void butter4_bandpass_sos(double lo, double hi, double fs, double out[4][6]) {
   for (int k = 0; k < 3; ++k) out[0][k] *= gain;
 }
 
+// scipy.signal.butter(4, fc / (fs / 2), 'high'): zpk2tf's b = k poly([1, 1, 1, 1]) = k (1, -4, 6, -4, 1) and
+// a = poly(p), here the product of the two sections' quadratics (the pole pairs are exact conjugates).
+void butter4_highpass_ba(double fc, double fs, double b[5], double a[5]) {
+  BiquadCoef s[2];
+  butter4_highpass_sos(fc, fs, s);
+  const double k = s[0].b[0];
+  const double pb[5] = {1.0, -4.0, 6.0, -4.0, 1.0};
+  for (int i = 0; i < 5; ++i) {
+    b[i] = k * pb[i];
+    a[i] = 0.0;
+  }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) a[i + j] += s[0].a[i] * s[1].a[j];
+}
+
+// scipy.signal.lfilter_zi: (I - companion(a).T) zi = b[1:] - a[1:] b[0]. The rows add up to
+// zi[0] sum(a) = sum(B); each following row then gives the next state.
+void lfilter_zi4(const double b[5], const double a[5], double zi[4]) {
+  double B[4], sb = 0.0, sa = a[0];
+  for (int i = 0; i < 4; ++i) {
+    B[i] = b[i + 1] - a[i + 1] * b[0];
+    sb += B[i];
+    sa += a[i + 1];
+  }
+  zi[0] = sb / sa;
+  zi[1] = (1.0 + a[1]) * zi[0] - B[0];
+  zi[2] = a[2] * zi[0] + zi[1] - B[1];
+  zi[3] = a[3] * zi[0] + zi[2] - B[2];
+}
+
+static void mat4_mul(const double* A, const double* B, double* C) {
+  double t[16];
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < 4; ++k) s += A[i * 4 + k] * B[k * 4 + j];
+      t[i * 4 + j] = s;
+    }
+  std::memcpy(C, t, sizeof t);
+}
+
+// z' = A z + B u with A = companion(a).T: P = A^L carries a state over a chunk of L samples
+void lfilter4_scan(const double a[5], int L, TdScan* out) {
+  const double A[16] = {-a[1], 1, 0, 0, -a[2], 0, 1, 0, -a[3], 0, 0, 1, -a[4], 0, 0, 0};
+  double P[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  for (int i = 0; i < L; ++i) mat4_mul(A, P, P);
+  std::memcpy(out->Pd[0], P, sizeof P);
+  for (int k = 1; k < 6; ++k) mat4_mul(out->Pd[k - 1], out->Pd[k - 1], out->Pd[k]);
+  mat4_mul(out->Pd[5], out->Pd[5], out->P64);
+  std::memcpy(out->Pl[0], P, sizeof P);
+  for (int l = 1; l < 64; ++l) mat4_mul(P, out->Pl[l - 1], out->Pl[l]);
+}
+
 void mat2_mul(const double* A, const double* B, double* C) {
   double t[4] = {A[0] * B[0] + A[1] * B[2], A[0] * B[1] + A[1] * B[3], A[2] * B[0] + A[3] * B[2],
                  A[2] * B[1] + A[3] * B[3]};

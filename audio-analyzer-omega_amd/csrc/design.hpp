@@ -27,6 +27,11 @@ BiquadCoef butter2(double fc, double fs, bool high);
 BiquadCoef butter1(double fc, double fs, bool high);
 void butter4_highpass_sos(double fc, double fs, BiquadCoef out[2]);
 void butter4_bandpass_sos(double lo, double hi, double fs, double out[4][6]);
+// scipy.signal.butter(4, fc / (fs / 2), 'high') in ba form, its lfilter_zi, and the carry-scan powers of the
+// order-4 DF2T recurrence's state matrix for chunks of L samples (tdetect.hip)
+void butter4_highpass_ba(double fc, double fs, double b[5], double a[5]);
+void lfilter_zi4(const double b[5], const double a[5], double zi[4]);
+void lfilter4_scan(const double a[5], int L, omega::TdScan* out);
 
 void mat2_mul(const double* A, const double* B, double* C);
 omega::BiquadTab make_biquad_tab(const BiquadCoef& c, int L);

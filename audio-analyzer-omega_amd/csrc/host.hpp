@@ -55,6 +55,7 @@ hipError_t launch_phase(const PhaseParams& p, hipStream_t s);
 hipError_t launch_room_modes(const RoomModesParams& p, hipStream_t s);
 hipError_t launch_room_rt60(const RoomRt60Params& p, hipStream_t s);
 hipError_t launch_voice(const VoiceParams& p, hipStream_t s);
+hipError_t launch_tdetect(const TdetectParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -148,6 +149,21 @@ struct VoiceState {
   bool set = false;
   VoiceParams p{};
   double* sg[4] = {};  // windows 5, 7, 9, 11
+};
+
+// capi_tdetect.cpp -- transient detection (omega_tdetect_configure / omega_tdetect_features): the configuration
+// with the band indices and the high-pass design (the stream state travels with the caller), the tables every
+// shape shares, the lfilter carry-scan table per (sample rate, frame length), the per-call workspace and the two
+// state blobs that chain a call's launches
+struct TdetectState {
+  bool set = false;
+  TdetectParams p{};
+  double* sg = nullptr;
+  double* han[2] = {};  // np.hanning(512), np.hanning(1024)
+  std::map<std::pair<double, int>, TdScan*> scans;
+  double* ws = nullptr;
+  int64_t ws_cap = 0;
+  double* chain[2] = {};
 };
 
 // capi_features.cpp -- the stream state of a feature that compares each frame's spectrum with the one
@@ -340,6 +356,7 @@ struct omega_ctx {
   PhaseState phase;
   RoomState room;
   VoiceState voice;
+  TdetectState tdetect;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables
@@ -459,6 +476,7 @@ int get_window(omega_ctx* c, int m, int kind, float** out);  // capi_core.cpp
 int get_rot(omega_ctx* c, int M, float2** out);              // capi_core.cpp
 void drop_graphs(omega_ctx* c);                              // capi_core.cpp (the graph cache emptied)
 int flush_meters(omega_ctx* c, hipStream_t on = nullptr);    // capi_batch.cpp
+int tr_pow2_tables(omega_ctx* c, int n, const double2** tw, const double2** tw2);  // capi_time.cpp
 
 // ---- host-memory staging (inline: omega_process_frames calls these on every step) ----
 // Page-locked host buffer of at least `bytes` (grown on demand; hipHostMalloc).

@@ -652,6 +652,54 @@ struct VoiceParams {
   double* out;              // [n_frames, kVoiceCols]
 };
 
+// TransientDetectionPanel's per-frame analysis (tdetect.hip; omega4/panels/transient_detection.py:79-365): one
+// launch of n_roles workgroups per frame (the role by blockIdx), then a small launch that forms the two
+// quantities that compare a frame with the ones before it (spectral flux, phase-deviation novelty)
+constexpr int kTdCols = 21;          // see include/omega.h for the columns
+constexpr int kTdThreads = 256;
+constexpr int kTdMinFrame = 256, kTdMaxFrame = 8192;
+constexpr int kTdMaxBins = 8193;
+constexpr double kTdMinRate = 8000.0;
+constexpr int kTdFluxLen = 512, kTdFluxBins = 128;     // :152, :166
+constexpr int kTdNovLen = 1024, kTdNovBins = 513;      // :324-332
+constexpr int kTdPad = 15;           // filtfilt's padlen 3 * max(len(a), len(b))
+// the carried state: has_spectrum, has_phase, two reserved words, the last flux spectrum, the last two phase rows
+constexpr int kTdStateLen = 4 + kTdFluxBins + 2 * kTdNovBins;
+// a frame's workspace row: non-finite flag, the flux spectrum's sum, the flux spectrum, the phases, the magnitudes
+constexpr int kTdWsStride = 2 + kTdFluxBins + 2 * kTdNovBins;
+enum TdRole : int { kTdEnvelope = 0, kTdFlux = 1, kTdNovelty = 2, kTdHf = 3, kTdScalar = 4, kTdRoles = 5 };
+// the order-4 lfilter carry scan (host-designed): P = A^L for the chunk length L, row-major 4 x 4
+struct TdScan {
+  double Pd[6][16];         // P^(2^k)
+  double P64[16];
+  double Pl[64][16];        // P^(lane + 1)
+};
+struct TdetectParams {
+  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values
+  int64_t spec_stride;
+  const void* audio;        // frame f at audio + f * audio_stride, m samples (float32, or float64 when f64)
+  int64_t audio_stride;
+  int64_t n_frames;
+  int f64;
+  int n_bins, m;
+  int n_roles;
+  int roles[kTdRoles];      // the roles launched, in grid order (workgroup b: roles[b / n_frames], frame b % n_frames)
+  int hf, nov;              // the shape has an HF column (m > 256, 5000 Hz below Nyquist) / a novelty (m >= 1024)
+  double bin_hz;            // rfftfreq's factor 1.0 / (2 (n_bins - 1) * (1 / fs)): freqs[k] = k * bin_hz
+  int band_idx[5];          // searchsorted(freqs, [0, 100, 250, 2000, fs / 2])
+  const double* sg;         // [11, 11] Savitzky-Golay (11, 3) weights by output position in the window
+  const double2 *tw_m, *tw2_m;      // the m-point real transform's tables (hilbert64.hpp)
+  const double2 *tw_f, *tw2_f;      // the 512-point one's
+  const double2 *tw_n, *tw2_n;      // the 1024-point one's
+  const double *han_f, *han_n;      // np.hanning(512), np.hanning(1024)
+  double b[5], a[5], zi[4]; // butter(4, 5000 / (fs / 2), 'high') in ba form and its lfilter_zi
+  const TdScan* scan;
+  double* ws;               // [n_frames, kTdWsStride]
+  const double* state_in;   // [kTdStateLen] or nullptr (a stream's first call)
+  double* state_out;        // [kTdStateLen] or nullptr
+  double* out;              // [n_frames, kTdCols]
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

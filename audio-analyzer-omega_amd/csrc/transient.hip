@@ -18,54 +18,10 @@
 // h = (1, 2, ..., 2, [1], 0, ...) -- on a complex mixed-radix transform in float64, then the same tail.
 #include <hip/hip_runtime.h>
 
+#include "hilbert64.hpp"
 #include "params.hpp"
 
 namespace omega {
-
-constexpr int kTrThreads = 256;
-
-__device__ __forceinline__ double2 zmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-// Stockham radix-2 forward FFT of K points: a -> (a, b ping-pong); returns the buffer holding X
-__device__ double2* tr_fft(double2* a, double2* b, int K, const double2* __restrict__ tw) {
-  for (int ns = 1; ns < K; ns <<= 1) {
-    const int step = K / (2 * ns);
-    for (int j = threadIdx.x; j < K / 2; j += kTrThreads) {
-      const int k = j & (ns - 1);
-      const double2 u = a[j], v = zmul(a[j + K / 2], tw[k * step]);
-      const int o = (j / ns) * 2 * ns + k;
-      b[o] = make_double2(u.x + v.x, u.y + v.y);
-      b[o + ns] = make_double2(u.x - v.x, u.y - v.y);
-    }
-    __syncthreads();
-    double2* t = a;
-    a = b;
-    b = t;
-  }
-  return a;
-}
-
-template <class T>
-__device__ __forceinline__ double block_sum_d(T v, double* red) {
-  double x = (double)v;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ __forceinline__ double block_max_d(double x, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
 
 // steps 4-6 on the envelope env[0..N) (es: the smoothed envelope's buffer), frame f
 __device__ __forceinline__ void transient_tail(const TransientParams& p, int64_t f, const double* env, double* es, double* red) {
@@ -158,48 +114,9 @@ __global__ __launch_bounds__(kTrThreads) void transient_kernel(TransientParams p
     const int64_t k = f * p.frame_stride + i;
     return p.f64 ? static_cast<const double*>(p.x)[k] : (double)static_cast<const float*>(p.x)[k];
   };
-  // 1) rfft of x as a K-point complex FFT of z[n] = x[2n] + i x[2n+1]
-  for (int k = threadIdx.x; k < K; k += kTrThreads) A[k] = make_double2(xin(2 * k), xin(2 * k + 1));
-  __syncthreads();
-  double2* Z = tr_fft(A, B, K, p.tw);
-  double2* Y = Z == A ? B : A;
-  // 2) X_k (k = 0..K) and Y_k = -i X_k, DC and Nyquist zeroed; then the packed inverse spectrum
-  //    Z'_k = (Y_k + conj Y_{K-k}) + i e^{2 pi i k / N} (Y_k - conj Y_{K-k}), stored conjugated so that
-  //    the forward FFT gives conj(K * ifft)
-  for (int k = threadIdx.x; k < K; k += kTrThreads) {
-    auto X = [&](int q) {  // rfft bin q in 0..K from the packed spectrum
-      const double2 a = Z[q % K], b = Z[(K - q) % K];
-      const double2 e = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));  // (Z_q + conj Z_{K-q}) / 2
-      const double2 o = make_double2(0.5 * (a.y + b.y), -0.5 * (a.x - b.x));  // (Z_q - conj Z_{K-q}) / 2i
-      const double2 w = p.tw2[q];                                             // e^{-2 pi i q / N}
-      const double2 ow = zmul(o, w);
-      return make_double2(e.x + ow.x, e.y + ow.y);
-    };
-    auto Yq = [&](int q) {
-      if (q == 0 || q == K) return make_double2(0.0, 0.0);
-      const double2 x = X(q);
-      return make_double2(x.y, -x.x);  // -i X
-    };
-    const double2 yk = Yq(k), ym = Yq(K - k);
-    const double2 s = make_double2(yk.x + ym.x, yk.y - ym.y);  // Y_k + conj Y_{K-k}
-    const double2 d = make_double2(yk.x - ym.x, yk.y + ym.y);  // Y_k - conj Y_{K-k}
-    const double2 w = p.tw2[k];                                 // conj e^{2 pi i k / N}
-    const double2 id = zmul(make_double2(-d.y, d.x), make_double2(w.x, -w.y));
-    Y[k] = make_double2(s.x + id.x, -(s.y + id.y));
-  }
-  __syncthreads();
-  double2* Bf = Y == A ? B : A;
-  double2* Hz = tr_fft(Y, Bf, K, p.tw);
-  // 3) envelope: H(x)[2n] = Re(ifft) / 2, H(x)[2n + 1] = Im(ifft) / 2, ifft = conj(FFT(conj)) / K
-  double* env = reinterpret_cast<double*>(Hz == A ? B : A);
-  const double sc = 0.5 / K;
-  for (int k = threadIdx.x; k < K; k += kTrThreads) {
-    const double h0 = Hz[k].x * sc, h1 = -Hz[k].y * sc;
-    const double x0 = xin(2 * k), x1 = xin(2 * k + 1);
-    env[2 * k] = sqrt(x0 * x0 + h0 * h0);
-    env[2 * k + 1] = sqrt(x1 * x1 + h1 * h1);
-  }
-  __syncthreads();
+  // 1-3) the envelope |hilbert(x)| (hilbert64.hpp)
+  double2* Hz = nullptr;
+  double* env = tr_hilbert_env(xin, N, A, B, p.tw, p.tw2, &Hz);
   transient_tail(p, f, env, reinterpret_cast<double*>(Hz), red);
 }
 

@@ -13,10 +13,11 @@ from .hip_hop_detector import HipHopDetector
 from .phase_correlation import PhaseCorrelation
 from .room_modes import RoomModeAnalyzer, RoomModeConfig
 from .voice_detection import VoiceDetectionPanel
+from .transient_detection import TransientDetectionPanel
 
 __all__ = [
     "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector", "PhaseCorrelation",
-    "RoomModeAnalyzer", "RoomModeConfig", "VoiceDetectionPanel",
+    "RoomModeAnalyzer", "RoomModeConfig", "VoiceDetectionPanel", "TransientDetectionPanel",
     "LIB_PATH", "OmegaError", "UnsupportedError", "lib", "Engine", "Resolution", "BandTable",
     "DEFAULT_RESOLUTIONS", "NORTHSTAR_RESOLUTIONS", "METER_KEYS",
     "CepstralAnalyzer", "PitchDetectionConfig", "get_preset_config", "list_presets",

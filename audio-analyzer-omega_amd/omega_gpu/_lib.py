@@ -81,6 +81,10 @@ class VoiceConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_double), ("n_bins", C.c_int32), ("frame_len", C.c_int32)]
 
 
+class TdetectConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_double), ("n_bins", C.c_int32), ("frame_len", C.c_int32)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -152,6 +156,12 @@ EXPORTS = {
     "omega_voice_configure": (C.c_int, [C.c_void_p, C.POINTER(VoiceConfig)]),
     "omega_voice_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                        C.c_int64, C.c_void_p, C.c_int]),
+    "omega_tdetect_config_default": (None, [C.POINTER(TdetectConfig)]),
+    "omega_tdetect_band_indices": (C.c_int, [C.c_double, C.c_int32, C.c_void_p]),
+    "omega_tdetect_configure": (C.c_int, [C.c_void_p, C.POINTER(TdetectConfig)]),
+    "omega_tdetect_state_size": (C.c_int64, []),
+    "omega_tdetect_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -712,6 +712,60 @@ int omega_voice_configure(omega_ctx* ctx, const omega_voice_config* cfg);
 int omega_voice_features(omega_ctx* ctx, const float* spectra, int64_t spec_stride, const void* frames, int32_t f64,
                          int32_t m, int64_t frame_stride, int64_t n_frames, double* out, int mem);
 
+/* TransientDetectionPanel (omega4/panels/transient_detection.py:79-365) for consecutive frames of one stream: every
+ * frame-local quantity of update(), and the two that compare a frame with the ones before it (spectral flux,
+ * phase-deviation novelty). The context keeps nothing between calls: the caller carries the stream's state, a blob
+ * of omega_tdetect_state_size() float64 values (the last flux spectrum, the last two phase rows, validity flags),
+ * from state_out of one call to state_in of the next. state_in NULL: a stream's first frames. state_out NULL: not
+ * wanted. Both live where `mem` says and may be the same buffer. One call on F frames equals F one-frame calls
+ * chained through the blob, bit for bit. The entry points are additive to ABI 5.
+ * omega_tdetect_configure fixes the shape and may be repeated. Built: frame_len a power of two 256..8192, n_bins
+ * 2..OMEGA_TDETECT_MAX_BINS, sample_rate >= 8000; anything else returns OMEGA_EUNSUP and leaves the configured
+ * shape as it was.
+ * omega_tdetect_band_indices (no context, no device): idx[5] = np.searchsorted(freqs, [0, 100, 250, 2000, fs / 2])
+ * over freqs = np.fft.rfftfreq(2 (n_bins - 1), 1 / sample_rate) as numpy evaluates it.
+ * omega_tdetect_features: frame f has its spectrum (n_bins float32 magnitudes) at spectra + f*spec_stride and its
+ * frame_len samples (float32, widened exactly, or float64 when f64) at frames + f*frame_stride, both in elements;
+ * rows may overlap. All arithmetic is float64. out [n_frames, OMEGA_TDETECT_COLS] float64:
+ *    0 flags        bit 0: a non-finite sample or bin (every other column is 0, and the frame is passed over as a
+ *                   predecessor: the state goes on as if it had not come); bit 1: no HF column for this shape
+ *                   (frame_len 256, or 5000 Hz not below Nyquist); bit 2: no novelty for this shape (frame_len <
+ *                   1024); bit 3: no frame before this one, flux is 0; bit 4: no frame before this one, novelty is 0
+ *    1 envelope     mean(savgol_filter(abs(hilbert(x)), 11, 3))
+ *    2 peak         max |x|            3 energy       sum x^2
+ *    4 flux_sum     sum(S), S = abs(rfft(x[:512] * hanning(512)))[:128] (zero-padded at frame_len 256)
+ *    5 flux         sum(max(0, S - S_prev))
+ *    6 novelty      sum(mag * min(|phase - (2 phase_1 - phase_2)|, pi)) over the 513 bins of rfft(pre[-1024:] *
+ *                   hanning(1024)), pre[n] = x[n] - 0.97 x[n-1] with pre[0] = x[0]; a stream's second frame takes
+ *                   phase_2 = phase_1 as the reference seeds them; no phase is wrapped
+ *    7 mag_sum      sum(mag) of those bins (0 with bit 2)
+ *    8 hf_energy    sum(filtfilt(*butter(4, 5000 / (fs / 2), 'high'), x) ** 2) (0 with bit 1)
+ *    9 sign_diff    sum |diff(sign x)| (an integer; the zero-crossing rate is this over 2 frame_len)
+ *   10 peak_idx     the first argmax |x|
+ *   11 start_idx    the nearest i < peak_idx with |x_i| < 0.1 peak, else 0
+ *   12 end_idx      the nearest i > peak_idx with |x_i| < 0.1 peak, else frame_len - 1
+ *   13 spec_sum     sum(s)            14 spec_fsum   sum(freqs * s)
+ *   15 rolloff_idx  the first i whose float64 prefix sum reaches 0.85 spec_sum (0 where spec_sum <= 0)
+ *   16..19 band sums s[idx[b]:idx[b+1]], 0 where the band's guard bit is clear
+ *   20 guards       bit b: idx[b] < n_bins and idx[b+1] < n_bins (the reference keeps a band's old value otherwise)
+ * Sums of the spectrum agree with a float64 evaluation to 1e-12 relative; the transform- and filter-derived
+ * columns to 1e-9 (hf_energy relative to energy, novelty relative to pi mag_sum). */
+#define OMEGA_TDETECT_COLS 21
+#define OMEGA_TDETECT_MAX_BINS 8193
+typedef struct {
+  double sample_rate;
+  int32_t n_bins;     /* bins per spectrum (the app: 513) */
+  int32_t frame_len;  /* samples per audio frame (the app: 2048) */
+} omega_tdetect_config;
+/* 48000 Hz, 513 bins, 2048 samples. */
+void omega_tdetect_config_default(omega_tdetect_config* cfg);
+int omega_tdetect_band_indices(double sample_rate, int32_t n_bins, int32_t* idx);
+int omega_tdetect_configure(omega_ctx* ctx, const omega_tdetect_config* cfg);
+int64_t omega_tdetect_state_size(void);
+int omega_tdetect_features(omega_ctx* ctx, const float* spectra, int64_t spec_stride, const void* frames, int32_t f64,
+                           int64_t n_frames, int64_t frame_stride, const double* state_in, double* state_out,
+                           double* out, int mem);
+
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks
  * of chunk_size samples, s16 scaled by 1/32768), its per-chunk noise gate (:620-641: RMS, background
