@@ -56,6 +56,8 @@ hipError_t launch_room_modes(const RoomModesParams& p, hipStream_t s);
 hipError_t launch_room_rt60(const RoomRt60Params& p, hipStream_t s);
 hipError_t launch_voice(const VoiceParams& p, hipStream_t s);
 hipError_t launch_tdetect(const TdetectParams& p, hipStream_t s);
+hipError_t launch_basszoom_frames(const BassZoomParams& p, hipStream_t s);
+hipError_t launch_basszoom_track(const BassZoomParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -164,6 +166,16 @@ struct TdetectState {
   double* ws = nullptr;
   int64_t ws_cap = 0;
   double* chain[2] = {};
+};
+
+// capi_basszoom.cpp -- the bass zoom panel (omega_basszoom_configure / omega_basszoom_features): the configuration
+// with the bar mapping (the panel's state travels with the caller), np.hanning(n) per window length and the
+// 8192-entry twiddle table
+struct BassZoomState {
+  bool set = false;
+  BassZoomParams p{};
+  std::map<int, double*> win;
+  double2* tw = nullptr;
 };
 
 // capi_features.cpp -- the stream state of a feature that compares each frame's spectrum with the one
@@ -357,6 +369,7 @@ struct omega_ctx {
   RoomState room;
   VoiceState voice;
   TdetectState tdetect;
+  BassZoomState basszoom;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables

@@ -700,6 +700,31 @@ struct TdetectParams {
   double* out;              // [n_frames, kTdCols]
 };
 
+// BassZoomPanel's per-frame analysis (basszoom.hip; omega4/panels/bass_zoom.py:51-97, :141-232): one workgroup per
+// frame for the windowed 8192-point spectrum's 20..200 Hz bins and the scaled bars, then one workgroup that runs the
+// float32 bar recurrence and the peak hold over the call's frames in order
+constexpr int kBzFft = 8192;         // :143
+constexpr int kBzThreads = 256;
+constexpr int kBzMaxBars = 64, kBzMaxBins = 256;  // include/omega.h states both caps
+constexpr int kBzRowHead = 3;        // flags, bass_max, scale_factor, then n_bars compressed values
+constexpr int kBzStateLen = 3 * kBzMaxBars;       // bars, peaks, peak timestamps (each kBzMaxBars float64)
+struct BassZoomParams {
+  const void* frames;       // frame f at frames + f * frame_stride (float32, or float64 when f64)
+  int64_t frame_stride;
+  int64_t n_frames;
+  int f64;
+  int nw;                   // samples read per frame: min(frame_len, kBzFft)
+  int first_bin, n_valid, bins_per_bar, n_bars;
+  double comp[kBzMaxBars];  // 0.3 / 0.6 / 1.0 / 0.8 by the bar's centre frequency
+  const double* win;        // np.hanning(nw)
+  const double2* tw;        // [kBzFft] e^{-2 pi i j / kBzFft}
+  const double* times;      // [n_frames] each frame's time (the reference's time.time())
+  const double* state_in;   // [kBzStateLen] or nullptr (a new panel)
+  double* state_out;        // [kBzStateLen] or nullptr
+  double* rows;             // [n_frames, kBzRowHead + n_bars]
+  double *bars, *peaks, *peak_times;  // [n_frames, n_bars] each
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

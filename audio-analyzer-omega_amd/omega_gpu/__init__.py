@@ -14,10 +14,11 @@ from .phase_correlation import PhaseCorrelation
 from .room_modes import RoomModeAnalyzer, RoomModeConfig
 from .voice_detection import VoiceDetectionPanel
 from .transient_detection import TransientDetectionPanel
+from .bass_zoom import BassZoomPanel
 
 __all__ = [
     "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector", "PhaseCorrelation",
-    "RoomModeAnalyzer", "RoomModeConfig", "VoiceDetectionPanel", "TransientDetectionPanel",
+    "RoomModeAnalyzer", "RoomModeConfig", "VoiceDetectionPanel", "TransientDetectionPanel", "BassZoomPanel",
     "LIB_PATH", "OmegaError", "UnsupportedError", "lib", "Engine", "Resolution", "BandTable",
     "DEFAULT_RESOLUTIONS", "NORTHSTAR_RESOLUTIONS", "METER_KEYS",
     "CepstralAnalyzer", "PitchDetectionConfig", "get_preset_config", "list_presets",

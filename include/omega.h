@@ -41,6 +41,8 @@
  *                          omega4/analyzers/harmonic_metrics.py:51-357 (§8(f) row 6)
  *   omega_genre_*          GenreClassifier.extract_features            omega4/panels/genre_classification.py:175-422,
  *                          :600-783 (§8(f) row 7)
+ *   omega_basszoom_*       BassZoomPanel.setup_bass_mapping            omega4/panels/bass_zoom.py:51-97 and
+ *                          _process_bass_detail_internal               bass_zoom.py:141-232 (§8(f) row 12)
  *
  * Conventions:
  *   - every function returns 0 on success and a negative omega_status on error; the message is
@@ -765,6 +767,57 @@ int64_t omega_tdetect_state_size(void);
 int omega_tdetect_features(omega_ctx* ctx, const float* spectra, int64_t spec_stride, const void* frames, int32_t f64,
                            int64_t n_frames, int64_t frame_stride, const double* state_in, double* state_out,
                            double* out, int mem);
+
+/* BassZoomPanel (omega4/panels/bass_zoom.py:51-97, :141-232) for consecutive frames of one stream: the 20..200 Hz
+ * bars of a Hann-windowed 8192-point spectrum, their smoothing and their peak hold. The context keeps nothing
+ * between calls: the caller carries the panel's state, a blob of omega_basszoom_state_size() float64 values (64
+ * bar values, 64 peak values, 64 peak timestamps; the first n_bars of each are used, the float32 state widened
+ * exactly), from state_out of one call to state_in of the next. state_in NULL: a new panel (all zero). state_out
+ * NULL: not wanted. Both live where `mem` says and may be the same buffer. One call on F frames equals F one-frame
+ * calls chained through the blob, bit for bit. The entry points are additive to ABI 5.
+ * omega_basszoom_mapping (no context, no device) reproduces setup_bass_mapping: the bins k of np.fft.rfftfreq(8192,
+ * 1 / sample_rate), as numpy evaluates it, with 20 <= f <= 200 are first_bin .. first_bin + n_valid - 1; bar i holds
+ * bins_per_bar = max(1, n_valid / 31) of them (the last bar may hold fewer); freq_ranges[2 i], [2 i + 1] are its
+ * first and last bin's frequencies (the start not below the bar before's end) and compensation[i] is 0.3 / 0.6 /
+ * 1.0 / 0.8 for a centre below 60 / 100 / 150 Hz / else. freq_ranges (2 OMEGA_BASSZOOM_MAX_BARS values) and
+ * compensation (OMEGA_BASSZOOM_MAX_BARS values) may be NULL, as may every other output. OMEGA_EINVAL: a rate that is
+ * not positive and finite. OMEGA_EUNSUP: no valid bin (a rate above 1638400 Hz; the reference then shows one bar
+ * that never moves), more than OMEGA_BASSZOOM_MAX_BINS valid bins (rates below about 5760 Hz), or more than
+ * OMEGA_BASSZOOM_MAX_BARS bars (no rate within the bin cap gives more than 61).
+ * omega_basszoom_configure fixes the shape and may be repeated. Built: frame_len >= 1 (the first min(frame_len,
+ * 8192) samples are read) at every rate the mapping accepts; frame_len 0 and every other rate return OMEGA_EUNSUP
+ * and leave the configured shape as it was.
+ * omega_basszoom_features: frame f has its samples (float32, widened exactly, or float64 when f64) at frames +
+ * f*frame_stride, in elements; rows may overlap. times[f] is frame f's time in seconds (the reference reads
+ * time.time() once per processed frame). All spectrum arithmetic is float64. Outputs, all float64:
+ *   rows [n_frames, 3 + n_bars]   0 flags: bit 0, a non-finite sample (every other column is 0 and the frame is
+ *                                 passed over: the state goes on as if it had not come)
+ *                                 1 bass_max: the largest compensated bar mean of abs(rfft(x[:n] * hanning(n), 8192)),
+ *                                 n = min(frame_len, 8192)
+ *                                 2 scale_factor: 0.85 / bass_max * (log10(max(1, 10 bass_max)) / 2), 1 at bass_max 0
+ *                                 3.. the bars scaled by it, those above 0.7 compressed to 0.7 + 0.3 (v - 0.7)
+ *   bars, peaks, peak_times [n_frames, n_bars]   bar_values, peak_values (float32 values) and peak_timestamps
+ *                                 after frame f: a rising bar takes 0.1 bar + 0.9 c, a falling one 0.6 bar + 0.4 c,
+ *                                 clamped to [0, 1], in numpy 2.x's types (float32 products bar * float32(0.1),
+ *                                 float64 products c * 0.9, their float64 sum rounded to float32); a bar above its
+ *                                 peak sets the peak and its timestamp, else the peak takes the float32 product
+ *                                 peak * float32(0.95) once times[f] - timestamp > 3.0
+ * bass_max, scale_factor and the compressed values agree with a float64 evaluation to 1e-9 of the row's largest. */
+#define OMEGA_BASSZOOM_MAX_BARS 64
+#define OMEGA_BASSZOOM_MAX_BINS 256
+typedef struct {
+  double sample_rate;
+  int32_t frame_len;  /* samples per audio frame (the app: 8192 and more) */
+} omega_basszoom_config;
+/* 48000 Hz, 8192 samples. */
+void omega_basszoom_config_default(omega_basszoom_config* cfg);
+int omega_basszoom_mapping(double sample_rate, int32_t* n_bars, int32_t* first_bin, int32_t* bins_per_bar,
+                           int32_t* n_valid, double* freq_ranges, double* compensation);
+int omega_basszoom_configure(omega_ctx* ctx, const omega_basszoom_config* cfg);
+int64_t omega_basszoom_state_size(void);
+int omega_basszoom_features(omega_ctx* ctx, const void* frames, int64_t frame_stride, int32_t f64, const double* times,
+                            int64_t n_frames, const double* state_in, double* rows, double* bars, double* peaks,
+                            double* peak_times, double* state_out, int mem);
 
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks
