@@ -27,26 +27,20 @@
 // non-finite are passed over and their output rows repeat the state.
 #include <hip/hip_runtime.h>
 
-#include "hilbert64.hpp"
 #include "params.hpp"
+#include "wg64.hpp"
 
 namespace omega {
 
 namespace {
 
 constexpr int kT = kBzThreads;
-static_assert(kBzThreads == kTrThreads, "hilbert64.hpp's reductions are for 256 threads");
+static_assert(kBzThreads == 4 * 64, "block_sum's default is four waves");
 constexpr int kBzGroup = 8;  // bins a wave holds at once
 
 __device__ __forceinline__ double bz_x(const BassZoomParams& p, int64_t f, int i) {
   const int64_t k = f * p.frame_stride + i;
   return p.f64 ? static_cast<const double*>(p.frames)[k] : (double)static_cast<const float*>(p.frames)[k];
-}
-
-__device__ __forceinline__ double wave_sum_d(double x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
 }
 
 // the row's tail from the magnitudes (:168-210), in the reference's operation order and without contraction
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(kT) void basszoom_frame_kernel(BassZoomParams p) {
     }
     bz_xw[i] = v;
   }
-  if (block_sum_d(bad, red) > 0.0) {  // (uniform; the barriers publish bz_xw)
+  if (block_sum(bad, red) > 0.0) {  // (uniform; the barriers publish bz_xw)
     if (t < kBzRowHead + p.n_bars) row[t] = t == 0 ? 1.0 : 0.0;
     return;
   }
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(kT) void basszoom_frame_kernel(BassZoomParams p) {
 #pragma unroll
     for (int j = 0; j < kBzGroup; ++j) {
       const double2 r = zmul(make_double2(sr[j], si[j]), p.tw[(k[j] * lane) & (kBzFft - 1)]);
-      const double re = wave_sum_d(r.x), im = wave_sum_d(r.y);
+      const double re = wave_sum(r.x), im = wave_sum(r.y);
       const int q = g * kBzGroup + j;
       if (lane == 0 && q < p.n_valid) mag[q] = hypot(re, im);
     }

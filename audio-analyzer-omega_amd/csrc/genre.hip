@@ -28,10 +28,11 @@
 //     :852      rms: float32 input np.sqrt(np.mean(x ** 2)) bit for bit, float64 input in float64
 #include <hip/hip_runtime.h>
 
+#pragma clang fp contract(off)  // (above the project headers: numpy_emul.hpp and wg64.hpp take this state)
+
 #include "numpy_emul.hpp"
 #include "params.hpp"
-
-#pragma clang fp contract(off)
+#include "wg64.hpp"
 
 namespace omega {
 
@@ -39,17 +40,8 @@ namespace {
 
 constexpr int kGT = kGenreThreads;
 constexpr int kGnSums = 12;        // np.sum(mag), the flux sum, np.sum(mag ** 2), nine band energies
-constexpr int kGnMaxLeaves = 136;  // numpy's pairwise leaves hold 64..128 elements: at most 128 for 8193
 constexpr int kGnWork = kGT - 64;  // the lanes of waves 1..3
 
-__device__ __forceinline__ double gn_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 __device__ __forceinline__ unsigned long long gn_max_u64(unsigned long long v, unsigned long long* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -136,31 +128,17 @@ __device__ __forceinline__ void gn_audio(const GenreParams& p, int64_t f, double
     }
     sq += (double)v * (double)v;
   }
-  bad = gn_sum(bad, red);
+  bad = block_sum(bad, red);
   if (bad > 0.0) {  // (uniform) the combine kernel zeroes the row
     if (t == 0) o[3] = -1.0;
     return;
   }
-  zc = gn_sum(zc, red);
-  sq = gn_sum(sq, red);
+  zc = block_sum(zc, red);
+  sq = block_sum(sq, red);
   double rms;
   if constexpr (sizeof(T) == 4) {
-    // np.sqrt(np.mean(x ** 2)): float32 squares, numpy's pairwise sum, float32(float64(sum) / m)
-    if (t == 0) {
-      int nl = 0;
-      np_emit_leaves<7>(0, m, ltab, nl);
-      pick[2] = nl;
-    }
-    __syncthreads();
-    const int nl = pick[2];
-    if (t < nl) {
-      const float* a = reinterpret_cast<const float*>(keys) + (ltab[t] & 0xFFFFu);
-      lsum[t] = np_slice_leaf((int)(ltab[t] >> 16), [&](int i) { return a[i] * a[i]; });
-    }
-    __syncthreads();
-    int idx = 0;
-    const float s = np_leaf_combine<7>(m, lsum, idx);  // (every lane: a broadcast read)
-    rms = (double)np_sqrt_f32((float)((double)s / (double)m));
+    // (|x| from the keys: the squares are the same)
+    rms = (double)np_rms_f32(reinterpret_cast<const float*>(keys), m, ltab, lsum, &pick[2]);
   } else {
     rms = sqrt(sq / (double)m);
   }
@@ -192,8 +170,8 @@ __global__ __launch_bounds__(kGT) void genre_kernel(GenreParams p) {
   __shared__ int hist[kGT];
   __shared__ int sh[4];
   __shared__ int pick[4];
-  __shared__ unsigned ltab[kGnSums * kGnMaxLeaves];
-  __shared__ float lsum[kGnSums * kGnMaxLeaves];
+  __shared__ unsigned ltab[kGnSums * kNpMaxLeaves];
+  __shared__ float lsum[kGnSums * kNpMaxLeaves];
   __shared__ int nleaf[kGnSums];
   __shared__ float sres[kGnSums];
   __shared__ int pk[kGenrePeaks];
@@ -232,10 +210,10 @@ __global__ __launch_bounds__(kGT) void genre_kernel(GenreParams p) {
   if (t < kGnSums) {
     const int lo = t < 3 ? 0 : p.band_lo[t - 3], n = t < 3 ? K : p.band_n[t - 3];
     int nl = 0;
-    if (n > 0) np_emit_leaves<7>(lo, n, ltab + t * kGnMaxLeaves, nl);
+    if (n > 0) np_emit_leaves<7>(lo, n, ltab + t * kNpMaxLeaves, nl);
     nleaf[t] = nl;
   }
-  bad = gn_sum(bad, red);  // (the barriers publish mag, ltab and nleaf)
+  bad = block_sum(bad, red);  // (the barriers publish mag, ltab and nleaf)
   if (bad > 0.0) {         // (uniform) the combine kernel zeroes the row
     if (t == 0) o[14] = -1.0;
     if (t < kGenrePeaks) pb[t] = -1;
@@ -263,9 +241,9 @@ __global__ __launch_bounds__(kGT) void genre_kernel(GenreParams p) {
     }
   } else if (t >= 64) {
     const int u = t - 64;
-    for (int l = u; l < kGnSums * kGnMaxLeaves; l += kGnWork) {
-      const int s = l / kGnMaxLeaves;
-      if (l - s * kGnMaxLeaves >= nleaf[s]) continue;
+    for (int l = u; l < kGnSums * kNpMaxLeaves; l += kGnWork) {
+      const int s = l / kNpMaxLeaves;
+      if (l - s * kNpMaxLeaves >= nleaf[s]) continue;
       const int off = (int)(ltab[l] & 0xFFFFu), n = (int)(ltab[l] >> 16);
       const float* a = mag + off;
       float r;
@@ -298,15 +276,15 @@ __global__ __launch_bounds__(kGT) void genre_kernel(GenreParams p) {
       if (prev && !isfinite(prev[i])) pbad = 1.0;
     }
   }
-  sfx = gn_sum(sfx, red);  // (the barriers publish cs and lsum)
-  slog = gn_sum(slog, red);
-  sam = gn_sum(sam, red);
-  cnt = gn_sum(cnt, red);
-  pbad = gn_sum(pbad, red);
+  sfx = block_sum(sfx, red);  // (the barriers publish cs and lsum)
+  slog = block_sum(slog, red);
+  sam = block_sum(sam, red);
+  cnt = block_sum(cnt, red);
+  pbad = block_sum(pbad, red);
   if (t < kGnSums) {
     const int n = t < 3 ? K : p.band_n[t - 3];
     int idx = 0;
-    sres[t] = n > 0 ? np_leaf_combine<7>(n, lsum + t * kGnMaxLeaves, idx) : 0.f;
+    sres[t] = n > 0 ? np_leaf_combine<7>(n, lsum + t * kNpMaxLeaves, idx) : 0.f;
   }
   __syncthreads();
   const float sabs = sres[0];
@@ -316,7 +294,7 @@ __global__ __launch_bounds__(kGT) void genre_kernel(GenreParams p) {
     const double d = fr[i] - centroid;
     var += (d * d) * (double)mag[i];
   }
-  var = gn_sum(var, red);
+  var = block_sum(var, red);
   // rolloff: the first index with cumsum >= float32(0.85) * cumsum[-1]
   const float ctot = cs[K - 1], cthr = __fmul_rn(0.85f, ctot);
   unsigned long long first = 0;

@@ -38,10 +38,11 @@
 // own error.
 #include <hip/hip_runtime.h>
 
+#pragma clang fp contract(off)  // (above the project headers: numpy_emul.hpp and wg64.hpp take this state)
+
 #include "numpy_emul.hpp"
 #include "params.hpp"
-
-#pragma clang fp contract(off)
+#include "wg64.hpp"
 
 namespace omega {
 
@@ -50,29 +51,10 @@ namespace {
 constexpr int kHT = kHarmonicThreads;
 constexpr int kHmDistance = 10;     // find_peaks(distance=10): a kept peak removes those < 10 bins away
 constexpr int kHmMaxPeaks = 832;    // kept peaks are >= 10 bins apart: at most ceil(8193 / 10) = 820
-constexpr int kHmMaxLeaves = 136;   // numpy's pairwise leaves hold 64..128 elements: at most 128 for 8193
 constexpr int kHmMaxIter = 200;
 constexpr double kHmRootTol = 1e-10;
 constexpr double kHmRealTol = 1e-8;
 constexpr double kHmTwoPi = 2.0 * 3.14159265358979323846;
-
-__device__ __forceinline__ double hm_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ double hm_max(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-__device__ __forceinline__ int hm_min_i(int v, double* red) { return (int)-hm_max(-(double)v, red); }
 
 // np.argmin(np.abs(freqs - target)) for the strictly increasing table: the first index at or above the
 // target by bisection (14 halvings cover 8193 entries), then the actual distances of the entries around
@@ -100,46 +82,7 @@ __device__ __forceinline__ int hm_nearest(const double* __restrict__ fr, int K, 
   return best;
 }
 
-// numpy's pairwise_sum of |a[i]| (float32): the leaves of the recursion in depth-first order, one
-// leaf's sum, and numpy_emul.hpp's np_leaf_combine for the tree
-template <int D>
-__device__ __forceinline__ void hm_emit_leaves(int off, int n, unsigned* tab, int& idx) {
-  if constexpr (D == 0) {
-    tab[idx++] = (unsigned)off | ((unsigned)n << 16);
-  } else {
-    if (n <= 128) {
-      tab[idx++] = (unsigned)off | ((unsigned)n << 16);
-      return;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    hm_emit_leaves<D - 1>(off, n2, tab, idx);
-    hm_emit_leaves<D - 1>(off + n2, n - n2, tab, idx);
-  }
-}
-__device__ __forceinline__ float hm_leaf_abs(const float* a, int n) {
-  if (n < 8) {
-    float r = 0.f;
-    for (int i = 0; i < n; ++i) r += fabsf(a[i]);
-    return r;
-  }
-  float r0 = fabsf(a[0]), r1 = fabsf(a[1]), r2 = fabsf(a[2]), r3 = fabsf(a[3]);
-  float r4 = fabsf(a[4]), r5 = fabsf(a[5]), r6 = fabsf(a[6]), r7 = fabsf(a[7]);
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-    r0 += fabsf(a[i]), r1 += fabsf(a[i + 1]), r2 += fabsf(a[i + 2]), r3 += fabsf(a[i + 3]);
-    r4 += fabsf(a[i + 4]), r5 += fabsf(a[i + 5]), r6 += fabsf(a[i + 6]), r7 += fabsf(a[i + 7]);
-  }
-  float res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-  for (; i < n; ++i) res += fabsf(a[i]);
-  return res;
-}
-
-struct HmZ {
-  double x, y;
-};
-__device__ __forceinline__ HmZ hm_zmul(HmZ a, HmZ b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ HmZ hm_zdiv(HmZ a, HmZ b) {
+__device__ __forceinline__ double2 hm_zdiv(double2 a, double2 b) {
   const double d = b.x * b.x + b.y * b.y;
   return {(a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d};
 }
@@ -163,8 +106,8 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
   __shared__ double dv[16];
   __shared__ double tots[kHT];
   __shared__ int icnt[kHT];
-  __shared__ unsigned ltab[kHmMaxLeaves];
-  __shared__ float lsum[kHmMaxLeaves];
+  __shared__ unsigned ltab[kNpMaxLeaves];
+  __shared__ float lsum[kNpMaxLeaves];
   __shared__ double ca[16], cn[16], rr[16], fmt[4];
   const int t = threadIdx.x;
   const int64_t f = blockIdx.x >> 1;
@@ -197,8 +140,8 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
       if (!isfinite(v)) bad = 1.0;
       mx = fmax(mx, (double)v);
     }
-    const double nbad = hm_sum(bad, red);
-    mx = hm_max(mx, red);
+    const double nbad = block_sum(bad, red);
+    mx = block_max(mx, red);
     int count = 0;
     int npk = 0;
     if (nbad == 0.0) {
@@ -303,7 +246,7 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
         ord[rank] = q;
         mykept += 1.0;
       }
-      count = (int)hm_sum(mykept, red);
+      count = (int)block_sum(mykept, red);
     }
     // ---- the series arrays: the top max_series, the rest -1 / 0 ----
     if (sb || ss) {
@@ -404,20 +347,23 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
         else pbad = 1.0;  // (a stored non-finite spectrum: its bins are left out and the frame is flagged)
       }
     }
-    pbad = hm_sum(pbad, red);
-    sfx = hm_sum(sfx, red);
-    nonf = hm_sum(nonf, red);
-    noise = hm_sum(noise, red);
-    flux = hm_sum(flux, red);
+    pbad = block_sum(pbad, red);
+    sfx = block_sum(sfx, red);
+    nonf = block_sum(nonf, red);
+    noise = block_sum(noise, red);
+    flux = block_sum(flux, red);
     // np.sum(|x|) in float32, numpy's pairwise order: one leaf per thread, the tree on thread 0
     if (t == 0) {
       int nl = 0;
-      hm_emit_leaves<7>(0, K, ltab, nl);
+      np_emit_leaves<7>(0, K, ltab, nl);
       si[16] = nl;
     }
     __syncthreads();
     const int nl = si[16];
-    if (t < nl) lsum[t] = hm_leaf_abs(spec + (ltab[t] & 0xFFFFu), (int)(ltab[t] >> 16));
+    if (t < nl) {
+      const float* a = spec + (ltab[t] & 0xFFFFu);
+      lsum[t] = np_slice_leaf((int)(ltab[t] >> 16), [&](int i) { return fabsf(a[i]); });
+    }
     __syncthreads();
     if (t == 0) {
       int idx = 0;
@@ -431,7 +377,7 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
       const double d = fr[i] - centroid;
       var += (d * d) * fabs((double)spec[i]);
     }
-    var = hm_sum(var, red);
+    var = block_sum(var, red);
     // rolloff: np.cumsum(|x|) >= 0.85 cumsum[-1], the first index
     const int C = (K + kHT - 1) / kHT;
     const int c0 = min(t * C, K), c1 = min(c0 + C, K);
@@ -450,7 +396,7 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
       run += fabs((double)spec[i]);
       if (run >= thr && first == 0x7fffffff) first = i;
     }
-    first = hm_min_i(first, red);
+    first = block_min_i(first, red);
     if (t == 0) {
       double he = 0.0;
 #pragma unroll
@@ -497,8 +443,8 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
     amax = fmax(amax, fabs(x));
     w[i] = (i ? x - 0.97 * raw(i - 1) : x) * p.ham[i];
   }
-  bad = hm_sum(bad, red);
-  amax = hm_max(amax, red);  // (the barriers publish w)
+  bad = block_sum(bad, red);
+  amax = block_max(amax, red);  // (the barriers publish w)
   if (bad > 0.0 || amax < 1e-10) {
     if (t < 5) o[10 + t] = t == 0 && bad > 0.0 ? -2.0 : 0.0;
     return;
@@ -513,7 +459,7 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
   }
 #pragma unroll
   for (int k = 0; k <= kHarmonicLpcOrder; ++k) {
-    const double r = hm_sum(acc[k], red);
+    const double r = block_sum(acc[k], red);
     if (t == 0) rr[k] = r;
   }
   __syncthreads();
@@ -541,30 +487,30 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
   if (!(rad >= 0.5)) rad = 0.5;
   if (rad > 2.0) rad = 2.0;
   const double ang0 = kHmTwoPi * (lane_on ? t : 0) / kHarmonicLpcOrder + 0.7;  // (off the real axis' symmetry)
-  HmZ z{rad * cos(ang0), rad * sin(ang0)};
+  double2 z{rad * cos(ang0), rad * sin(ang0)};
   int done = 0, extra = 0;
 #pragma unroll 1
   for (int it = 0; it < kHmMaxIter; ++it) {
-    HmZ pv{1.0, 0.0}, dp{0.0, 0.0};
+    double2 pv{1.0, 0.0}, dp{0.0, 0.0};
 #pragma unroll 1
     for (int k = 1; k <= kHarmonicLpcOrder; ++k) {
-      dp = hm_zmul(dp, z);
+      dp = zmul(dp, z);
       dp.x += pv.x, dp.y += pv.y;
-      pv = hm_zmul(pv, z);
+      pv = zmul(pv, z);
       pv.x += ca[k];
     }
-    HmZ S{0.0, 0.0};
+    double2 S{0.0, 0.0};
 #pragma unroll 1
     for (int k = 0; k < kHarmonicLpcOrder; ++k) {
-      const HmZ zk{__shfl(z.x, k, 64), __shfl(z.y, k, 64)};
+      const double2 zk{__shfl(z.x, k, 64), __shfl(z.y, k, 64)};
       if (k != t) {
-        const HmZ q = hm_zdiv(HmZ{1.0, 0.0}, HmZ{z.x - zk.x, z.y - zk.y});
+        const double2 q = hm_zdiv(double2{1.0, 0.0}, double2{z.x - zk.x, z.y - zk.y});
         S.x += q.x, S.y += q.y;
       }
     }
-    const HmZ nt = hm_zdiv(pv, dp);
-    const HmZ ns = hm_zmul(nt, S);
-    const HmZ wv = hm_zdiv(nt, HmZ{1.0 - ns.x, -ns.y});
+    const double2 nt = hm_zdiv(pv, dp);
+    const double2 ns = zmul(nt, S);
+    const double2 wv = hm_zdiv(nt, double2{1.0 - ns.x, -ns.y});
     double upd = 0.0;
     if (lane_on) {
       z.x -= wv.x, z.y -= wv.y;

@@ -1,17 +1,16 @@
 // The float64 transform shared by transient.hip and tdetect.hip, for 256-thread workgroups: the radix-2
-// Stockham FFT in LDS with a float64 twiddle table, the real-signal (un)packing around it, |hilbert(x)| of a
-// power-of-two frame, and the block reductions.
+// Stockham FFT in LDS with a float64 twiddle table, the real-signal (un)packing around it and |hilbert(x)|
+// of a power-of-two frame. Like wg64.hpp, whose primitives it uses, it takes the including file's
+// floating-point contraction state.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "wg64.hpp"
+
 namespace omega {
 
 constexpr int kTrThreads = 256;
-
-__device__ __forceinline__ double2 zmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
 
 // Stockham radix-2 forward FFT of K points: a -> (a, b ping-pong); returns the buffer holding X
 // (tw: [K / 2] e^{-2 pi i m / K})
@@ -87,26 +86,6 @@ __device__ __forceinline__ double* tr_hilbert_env(XIn xin, int N, double2* A, do
   __syncthreads();
   *spare = Hz;
   return env;
-}
-
-template <class T>
-__device__ __forceinline__ double block_sum_d(T v, double* red) {
-  double x = (double)v;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ __forceinline__ double block_max_d(double x, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
 
 }  // namespace omega

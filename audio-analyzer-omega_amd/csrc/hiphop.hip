@@ -26,131 +26,30 @@
 //
 // LDS: the audio role holds the frame as m float64 samples and, for the envelope, a second buffer of m / 2
 // complex values: the Hilbert transform is the packed real FFT pair of transient.hip run in place
-// (decimation in frequency to bit-reversed order, decimation in time back, as in pitch.hip), so filters
+// (decimation in frequency to bit-reversed order, decimation in time back: wg64.hpp's pair), so filters
 // and envelope are ONE kernel of 16 m bytes (plus 4 KiB of carries and 11.6 KiB static): 143 KiB at m = 8192
 // (one workgroup per CU), 47 KiB at m = 2048 (three per CU). The peak flags reuse the transform buffer.
 //
-// Each cascade section is weight64.hip's chunked scan as pitch.hip runs it: every thread runs its chunk of
-// ceil(m / 256) samples from the zero state, the chunk end states are combined over the workgroup with
-// the powers of P = A^chunk, and every thread re-runs its chunk from its true incoming state. At m = 64
-// and 128 the chunk is one sample and only the first m threads own one; the others carry a zero state
-// that no owning thread reads. A zero input prefix gives exact zeros either way (0 * c + 0).
+// Each cascade section is wg64.hpp's chunked scan (sos_section_scan). At m = 64 and 128 the chunk is one
+// sample and only the first m threads own one; the others carry a zero state that no owning thread
+// reads. A zero input prefix gives exact zeros either way (0 * c + 0).
 //
 // Reductions: the float64 sums (filtered RMS, envelope mean and np.std) are lane-strided block sums, not
 // numpy's pairwise order; they agree with it to a few 1e-16 relative, far inside the 1e-9 the filters set.
 #include <hip/hip_runtime.h>
 
+#pragma clang fp contract(off)  // (above the project headers: numpy_emul.hpp and wg64.hpp take this state)
+
 #include "numpy_emul.hpp"
 #include "params.hpp"
-
-#pragma clang fp contract(off)
+#include "wg64.hpp"
 
 namespace omega {
 
 namespace {
 
 constexpr int kHT = kHipHopThreads;
-constexpr int kHhMaxLeaves = 136;     // numpy's pairwise leaves hold 64..128 elements: at most 128 for 8193
 constexpr int kHhVocalDistance = 20;  // find_peaks(distance=20): a kept peak removes those < 20 bins away
-
-__device__ __forceinline__ double2 hh_zmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double hh_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ double hh_max(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-__device__ __forceinline__ int hh_brev(int i, int bits) { return (int)(__brev((unsigned)i) >> (32 - bits)); }
-
-// K-point complex FFT in place, decimation in frequency: natural order in, X[q] at a[brev(q)] out.
-// tw[q] = e^{-2 pi i q / (2 K)}
-__device__ void hh_fft_dif(double2* a, int K, const double2* __restrict__ tw) {
-  for (int half = K / 2; half >= 1; half >>= 1) {
-    const int step = K / (2 * half);
-    for (int j = threadIdx.x; j < K / 2; j += kHT) {
-      const int k = j & (half - 1), i0 = (j - k) * 2 + k, i1 = i0 + half;
-      const double2 u = a[i0], v = a[i1];
-      a[i0] = make_double2(u.x + v.x, u.y + v.y);
-      a[i1] = hh_zmul(make_double2(u.x - v.x, u.y - v.y), tw[2 * k * step]);
-    }
-    __syncthreads();
-  }
-}
-// the same transform, decimation in time: element q at a[brev(q)] in, natural order out
-__device__ void hh_fft_dit(double2* a, int K, const double2* __restrict__ tw) {
-  for (int half = 1; half < K; half <<= 1) {
-    const int step = K / (2 * half);
-    for (int j = threadIdx.x; j < K / 2; j += kHT) {
-      const int k = j & (half - 1), i0 = (j - k) * 2 + k, i1 = i0 + half;
-      const double2 u = a[i0], v = hh_zmul(a[i1], tw[2 * k * step]);
-      a[i0] = make_double2(u.x + v.x, u.y + v.y);
-      a[i1] = make_double2(u.x - v.x, u.y - v.y);
-    }
-    __syncthreads();
-  }
-}
-
-struct HhM2 {
-  double a, b, c, d;
-};
-__device__ __forceinline__ HhM2 hh_mmul(const HhM2& x, const HhM2& y) {
-  return {x.a * y.a + x.b * y.c, x.a * y.b + x.b * y.d, x.c * y.a + x.d * y.c, x.c * y.b + x.d * y.d};
-}
-
-// scipy.signal.sosfilt's section (DF2T, zero initial state) over v[0..n) in place
-__device__ void hh_lfilter(double* v, int n, const double* cf, double2* sc) {
-  const int t = threadIdx.x;
-  const struct {
-    double b0, b1, b2, a1, a2;
-  } q{cf[0], cf[1], cf[2], cf[3], cf[4]};
-  const int L = (n + kHT - 1) / kHT;  // (n < 256: one sample, owned by the first n threads)
-  const int lo = min(t * L, n), hi = min(lo + L, n);
-  double z0 = 0.0, z1 = 0.0;
-  auto step = [&](double u) {
-    const double y = q.b0 * u + z0;
-    z0 = q.b1 * u + z1 - q.a1 * y;
-    z1 = q.b2 * u - q.a2 * y;
-    return y;
-  };
-  for (int k = lo; k < hi; ++k) step(v[k]);
-  // inclusive scan of the chunk end states, c_t = sum_j P^(t-j) e_j with P = A^L, A = [[-a1, 1], [-a2, 0]]
-  // (a thread without samples has e = 0 and lies past every thread that owns some: its c is not read)
-  HhM2 P{1.0, 0.0, 0.0, 1.0}, Ak{-q.a1, 1.0, -q.a2, 0.0};
-  for (int e = L; e; e >>= 1) {
-    if (e & 1) P = hh_mmul(P, Ak);
-    Ak = hh_mmul(Ak, Ak);
-  }
-  double2 c = make_double2(z0, z1);
-  for (int d = 1; d < kHT; d <<= 1) {
-    sc[t] = c;
-    __syncthreads();
-    if (t >= d) {
-      const double2 o = sc[t - d];
-      c = make_double2(c.x + (P.a * o.x + P.b * o.y), c.y + (P.c * o.x + P.d * o.y));
-    }
-    __syncthreads();
-    P = hh_mmul(P, P);
-  }
-  sc[t] = c;
-  __syncthreads();
-  const double2 s = t > 0 ? sc[t - 1] : make_double2(0.0, 0.0);
-  z0 = s.x;
-  z1 = s.y;
-  for (int k = lo; k < hi; ++k) v[k] = step(v[k]);
-  __syncthreads();
-}
 
 // scipy's _local_maxima_1d at plateau start i (0 < i < n - 1): the peak's index, or -1
 template <class T>
@@ -183,7 +82,10 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
     __syncthreads();
   };
   auto filter = [&](int which) {
-    for (int s = 0; s < 4; ++s) hh_lfilter(S, m, cf[which][s], sc);
+    for (int s = 0; s < 4; ++s) {
+      const double* c = cf[which][s];
+      sos_section_scan<kHT>(S, m, c[0], c[1], c[2], c[3], c[4], sc);
+    }
   };
   if (t == 0) {
 #pragma unroll
@@ -204,30 +106,15 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
     if (!isfinite(v)) bad = 1.0;
     sq += v * v;
   }
-  bad = hh_sum(bad, red);
+  bad = block_sum(bad, red);
   if (bad > 0.0) {  // (uniform) the combine kernel zeroes the row
     if (t == 0) o[4] = -1.0;
     return;
   }
-  sq = hh_sum(sq, red);
+  sq = block_sum(sq, red);
   double rms;
   if (!p.f64) {
-    // np.sqrt(np.mean(x ** 2)): float32 squares, numpy's pairwise sum, float32(float64(sum) / m)
-    if (t == 0) {
-      int nl = 0;
-      np_emit_leaves<7>(0, m, ltab, nl);
-      nl_s = nl;
-    }
-    __syncthreads();
-    const int nl = nl_s;
-    if (t < nl) {
-      const float* a = x32 + (ltab[t] & 0xFFFFu);
-      lsum[t] = np_slice_leaf((int)(ltab[t] >> 16), [&](int i) { return a[i] * a[i]; });
-    }
-    __syncthreads();
-    int idx = 0;
-    const float s = np_leaf_combine<7>(m, lsum, idx);  // (every lane: a broadcast read)
-    rms = (double)np_sqrt_f32((float)((double)s / (double)m));
+    rms = (double)np_rms_f32(x32, m, ltab, lsum, &nl_s);
   } else {
     rms = sqrt(sq / (double)m);
   }
@@ -241,7 +128,7 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
   filter(0);
   double s2 = 0.0;
   for (int i = t; i < m; i += kHT) s2 += S[i] * S[i];
-  const double sub_rms = sqrt(hh_sum(s2, red) / (double)m);
+  const double sub_rms = sqrt(block_sum(s2, red) / (double)m);
   // hi-hat (:268-276)
   load();
   filter(2);
@@ -256,8 +143,8 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
       zc += sa != sb;
     }
   }
-  const double hat_rms = sqrt(hh_sum(s2, red) / (double)m);
-  zc = hh_sum(zc, red);
+  const double hat_rms = sqrt(block_sum(s2, red) / (double)m);
+  zc = block_sum(zc, red);
   // kick (:226-229): H(x) = irfft(-i X), X = rfft(x) with DC and Nyquist zeroed, as two K-point complex
   // transforms of z[n] = x[2n] + i x[2n+1]
   load();
@@ -266,19 +153,19 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
   __syncthreads();
   int bits = 0;
   while ((1 << bits) < K) ++bits;
-  hh_fft_dif(Z, K, p.tw);
+  fft_dif<kHT>(Z, K, p.tw, 2);
   // X_q = (Z_q + conj Z_{K-q}) / 2 + e^{-2 pi i q / m} (Z_q - conj Z_{K-q}) / 2i, Y_q = -i X_q; the packed
   // inverse spectrum Z'_k = (Y_k + conj Y_{K-k}) + i e^{2 pi i k / m} (Y_k - conj Y_{K-k}), stored conjugated
   // so that the forward transform returns conj(K ifft). Bins k and K - k read and write the same two
   // slots, so one thread does the pair.
   for (int k = t; k <= K / 2; k += kHT) {
     const int mk = (K - k) & (K - 1);
-    const int pk = hh_brev(k, bits), pm = hh_brev(mk, bits);
+    const int pk = brev(k, bits), pm = brev(mk, bits);
     const double2 zk = Z[pk], zm = Z[pm];
     auto Y = [&](double2 za, double2 zb, int q) {  // -i X_q, za = Z_q, zb = Z_{K-q}
       const double2 e = make_double2(0.5 * (za.x + zb.x), 0.5 * (za.y - zb.y));
       const double2 od = make_double2(0.5 * (za.y + zb.y), -0.5 * (za.x - zb.x));
-      const double2 ow = hh_zmul(od, p.tw[q]);
+      const double2 ow = zmul(od, p.tw[q]);
       return make_double2(e.y + ow.y, -(e.x + ow.x));
     };
     const double2 zero = make_double2(0.0, 0.0);
@@ -288,14 +175,14 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
       const double2 s = make_double2(ya.x + yb.x, ya.y - yb.y);
       const double2 d = make_double2(ya.x - yb.x, ya.y + yb.y);
       const double2 w = p.tw[q];
-      const double2 id = hh_zmul(make_double2(-d.y, d.x), make_double2(w.x, -w.y));
+      const double2 id = zmul(make_double2(-d.y, d.x), make_double2(w.x, -w.y));
       return make_double2(s.x + id.x, -(s.y + id.y));
     };
     Z[pk] = pack(yk, ym, k);
     if (mk != k) Z[pm] = pack(ym, yk, K - k);
   }
   __syncthreads();
-  hh_fft_dit(Z, K, p.tw);
+  fft_dit<kHT>(Z, K, p.tw, 2);
   // envelope: H(x)[2n] = Re(ifft) / 2, H(x)[2n + 1] = Im(ifft) / 2, ifft = conj(FFT(conj)) / K
   const double scl = 0.5 / K;
   double s1 = 0.0;
@@ -307,13 +194,13 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
     S[2 * k + 1] = e1;
     s1 += e0 + e1;
   }
-  const double mean = hh_sum(s1, red) / (double)m;  // (the barriers publish the envelope; Z is free)
+  const double mean = block_sum(s1, red) / (double)m;  // (the barriers publish the envelope; Z is free)
   s2 = 0.0;
   for (int i = t; i < m; i += kHT) {
     const double d = S[i] - mean;
     s2 += d * d;
   }
-  const double thr = mean + 1.5 * sqrt(hh_sum(s2, red) / (double)m);
+  const double thr = mean + 1.5 * sqrt(block_sum(s2, red) / (double)m);
   // find_peaks(envelope, height = thr, distance): candidates, then scipy's greedy distance rule
   int* cand = reinterpret_cast<int*>(Z);  // [m]
   for (int i = t; i < m; i += kHT) cand[i] = 0;
@@ -329,12 +216,12 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
     double best = -1.0;
     for (int i = t; i < m; i += kHT)
       if (cand[i]) best = fmax(best, S[i]);
-    best = hh_max(best, red);
+    best = block_max(best, red);
     if (best < 0.0) break;  // (uniform) none left
     int at = -1;
     for (int i = t; i < m; i += kHT)
       if (cand[i] && S[i] == best) at = max(at, i);
-    at = (int)hh_max((double)at, red);
+    at = (int)block_max((double)at, red);
     if (t == 0) kept[nk] = at;
     ++nk;
     for (int i = t; i < m; i += kHT)
@@ -385,8 +272,8 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
 // ---- role 0: the spectrum side ----
 __device__ __forceinline__ void hh_spectrum(const HipHopParams& p, int64_t f, double* o, unsigned char* smem) {
   __shared__ double red[4];
-  __shared__ unsigned ltab[kHipHopBands * kHhMaxLeaves];
-  __shared__ float lsum[kHipHopBands * kHhMaxLeaves];
+  __shared__ unsigned ltab[kHipHopBands * kNpMaxLeaves];
+  __shared__ float lsum[kHipHopBands * kNpMaxLeaves];
   __shared__ int nleaf[kHipHopBands];
   __shared__ float sres[kHipHopBands];
   __shared__ int blo[kHipHopBands], bn[kHipHopBands];  // (constant indices into the kernel argument)
@@ -414,24 +301,24 @@ __device__ __forceinline__ void hh_spectrum(const HipHopParams& p, int64_t f, do
   }
   if (t < kHipHopBands) {
     int nl = 0;
-    if (bn[t] > 0) np_emit_leaves<7>(blo[t], bn[t], ltab + t * kHhMaxLeaves, nl);
+    if (bn[t] > 0) np_emit_leaves<7>(blo[t], bn[t], ltab + t * kNpMaxLeaves, nl);
     nleaf[t] = nl;
   }
-  bad = hh_sum(bad, red);  // (the barriers publish mag, ltab and nleaf)
+  bad = block_sum(bad, red);  // (the barriers publish mag, ltab and nleaf)
   if (bad > 0.0) {         // (uniform) the combine kernel zeroes the row
     if (t == 0) o[7] = -1.0;
     return;
   }
-  for (int l = t; l < kHipHopBands * kHhMaxLeaves; l += kHT) {
-    const int s = l / kHhMaxLeaves;
-    if (l - s * kHhMaxLeaves >= nleaf[s]) continue;
+  for (int l = t; l < kHipHopBands * kNpMaxLeaves; l += kHT) {
+    const int s = l / kNpMaxLeaves;
+    if (l - s * kNpMaxLeaves >= nleaf[s]) continue;
     const float* a = mag + (ltab[l] & 0xFFFFu);
     lsum[l] = np_slice_leaf((int)(ltab[l] >> 16), [&](int i) { return a[i] * a[i]; });
   }
   __syncthreads();
   if (t < kHipHopBands) {
     int idx = 0;
-    sres[t] = bn[t] > 0 ? np_leaf_combine<7>(bn[t], lsum + t * kHhMaxLeaves, idx) : 0.f;
+    sres[t] = bn[t] > 0 ? np_leaf_combine<7>(bn[t], lsum + t * kNpMaxLeaves, idx) : 0.f;
   }
   __syncthreads();
 
@@ -442,7 +329,7 @@ __device__ __forceinline__ void hh_spectrum(const HipHopParams& p, int64_t f, do
   if (n > 10) {  // (uniform)
     double vm = 0.0;
     for (int i = t; i < n; i += kHT) vm = fmax(vm, (double)v[i]);
-    const float vmax = (float)hh_max(vm, red);
+    const float vmax = (float)block_max(vm, red);
     const double pmin = (double)__fmul_rn(vmax, 0.3f);  // np.max(.) * 0.3 is a float32, widened for the comparison
     int any = 0;
     for (int i = 1 + t; i < n - 1; i += kHT) {
@@ -483,7 +370,7 @@ __device__ __forceinline__ void hh_spectrum(const HipHopParams& p, int64_t f, do
       const double prom = (double)h - (double)fmaxf(lmin, rmin);
       if (pmin <= prom) npk += 1.0;
     }
-    npk = hh_sum(npk, red);
+    npk = block_sum(npk, red);
   }
   if (t == 0) {
     // :293-330

@@ -1,10 +1,14 @@
 // Device restatements of numpy's float32 reductions, for kernels that must reproduce numpy's
 // rounding bit for bit (the app post-processing, the capture noise gate). Include with floating-point
-// contraction off in the including file (#pragma clang fp contract(off)).
+// contraction off in the including file: its functions take the contraction state in force where this
+// header is included, so `#pragma clang fp contract(off)` stands ABOVE the #include (wg64.hpp has the rule).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace omega {
+
+// numpy's pairwise leaves hold 64..128 elements: at most 128 for 8193, the longest range summed here
+constexpr int kNpMaxLeaves = 136;
 
 // np.sqrt of a float32: the correctly rounded square root. The hardware square root (v_sqrt_f32,
 // what __fsqrt_rn lowers to here) is within 1 ulp, not correctly rounded (measured: 0.41999188 ->
@@ -122,6 +126,29 @@ __device__ __forceinline__ float np_slice_leaf(int n, Term term) {
   float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
   for (; i < n; ++i) res += term(i);
   return res;
+}
+
+// np.sqrt(np.mean(x ** 2)) of m <= 16384 float32 samples by the whole workgroup (at least as many threads
+// as leaves): float32 squares, numpy's pairwise sum (one leaf per thread, the tree on every lane from
+// broadcast reads), float32(float64(sum) / m). ltab, lsum: a slot per leaf; nl_s: one int. Two barriers;
+// every thread gets the value.
+__device__ __forceinline__ float np_rms_f32(const float* x, int m, unsigned* ltab, float* lsum, int* nl_s) {
+  const int t = threadIdx.x;
+  if (t == 0) {
+    int nl = 0;
+    np_emit_leaves<7>(0, m, ltab, nl);
+    *nl_s = nl;
+  }
+  __syncthreads();
+  const int nl = *nl_s;
+  if (t < nl) {
+    const float* a = x + (ltab[t] & 0xFFFFu);
+    lsum[t] = np_slice_leaf((int)(ltab[t] >> 16), [&](int i) { return a[i] * a[i]; });
+  }
+  __syncthreads();
+  int idx = 0;
+  const float s = np_leaf_combine<7>(m, lsum, idx);
+  return np_sqrt_f32((float)((double)s / (double)m));
 }
 
 // One wave's share of np_pairwise_sum(a, n): the leaf sums, one per leaf of the table, into

@@ -31,34 +31,16 @@
 // relative; the bar on what they feed is 1e-9 (include/omega.h).
 #include <hip/hip_runtime.h>
 
-#include "params.hpp"
+#pragma clang fp contract(off)  // (above the project headers: wg64.hpp takes this state)
 
-#pragma clang fp contract(off)
+#include "params.hpp"
+#include "wg64.hpp"
 
 namespace omega {
 
 namespace {
 
 constexpr int kPT = kPhaseThreads;
-
-__device__ __forceinline__ int ph_brev(int i, int bits) { return (int)(__brev((unsigned)i) >> (32 - bits)); }
-
-// block sums of N values at once (red: 4 N doubles); every thread gets every sum
-template <int N>
-__device__ __forceinline__ void ph_sum(double (&v)[N], double* red) {
-#pragma unroll
-  for (int n = 0; n < N; ++n)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[n] += __shfl_xor(v[n], o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int n = 0; n < N; ++n) red[(threadIdx.x >> 6) * N + n] = v[n];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int n = 0; n < N; ++n) v[n] = red[n] + red[N + n] + red[2 * N + n] + red[3 * N + n];
-}
 
 // :152-164 from the centred sums over n values; *flat: a std (or their product) was 0, the 0.0 fallback
 __device__ __forceinline__ double ph_corr(double cll, double crr, double clr, double n, bool* flat) {
@@ -101,7 +83,7 @@ __global__ __launch_bounds__(kPT) void phase_kernel(PhaseParams p) {
     a[1] += l;
     a[2] += r;
   }
-  ph_sum(a, red);  // (the barriers publish blo and bhi)
+  block_sums<3, 4>(a, red);  // (the barriers publish blo and bhi)
   if (a[0] > 0.0) {  // (uniform) a non-finite sample: the zero row, flag bit 0, no points
     if (t < kPhaseCols) o[t] = t == 5 ? 1.0 : 0.0;
     if (pts) pts[t] = 0.0;  // (kPT = 2 kPhasePoints)
@@ -121,7 +103,7 @@ __global__ __launch_bounds__(kPT) void phase_kernel(PhaseParams p) {
     c[4] += v.y * v.y;
     Z[slot(i)] = make_double2(v.x * w, v.y * w);
   }
-  ph_sum(c, red);  // (the barriers publish the windowed frame)
+  block_sums<5, 4>(c, red);  // (the barriers publish the windowed frame)
 
   // :169-177 every step-th sample, straight from the input
   if (pts && t < kPhasePoints) {
@@ -138,20 +120,10 @@ __global__ __launch_bounds__(kPT) void phase_kernel(PhaseParams p) {
   }
 
   // the m-point transform in place, decimation in frequency
-  for (int half = m / 2; half >= 1; half >>= 1) {
-    const int step = m / (2 * half);
-    for (int j = t; j < m / 2; j += kPT) {
-      const int k = j & (half - 1), i0 = slot((j - k) * 2 + k), i1 = slot((j - k) * 2 + k + half);
-      const double2 u = Z[i0], v = Z[i1], w = p.tw[k * step];
-      const double2 d = make_double2(u.x - v.x, u.y - v.y);
-      Z[i0] = make_double2(u.x + v.x, u.y + v.y);
-      Z[i1] = make_double2(d.x * w.x - d.y * w.y, d.x * w.y + d.y * w.x);
-    }
-    __syncthreads();
-  }
+  fft_dif<kPT>(Z, m, p.tw, 1, slot);
   // bins k and m - k give |L_k| and |R_k|, stored over Z_k: no other thread touches either slot
   for (int k = t; k <= m / 2; k += kPT) {
-    const int pk = slot(ph_brev(k, bits)), pm = slot(ph_brev((m - k) & (m - 1), bits));
+    const int pk = slot(brev(k, bits)), pm = slot(brev((m - k) & (m - 1), bits));
     const double2 zk = Z[pk], zm = Z[pm];
     const double lx = 0.5 * (zk.x + zm.x), ly = 0.5 * (zk.y - zm.y);
     const double rx = 0.5 * (zk.y + zm.y), ry = -0.5 * (zk.x - zm.x);
@@ -164,12 +136,11 @@ __global__ __launch_bounds__(kPT) void phase_kernel(PhaseParams p) {
   for (int b = 0; b < kPhaseBands; ++b) {
     double s0 = 0.0, s1 = 0.0;
     for (int k = blo[b] + t; k < bhi[b]; k += kPT) {
-      const double2 g = Z[slot(ph_brev(k, bits))];
+      const double2 g = Z[slot(brev(k, bits))];
       s0 += g.x;
       s1 += g.y;
     }
-#pragma unroll
-    for (int q = 32; q > 0; q >>= 1) s0 += __shfl_xor(s0, q, 64), s1 += __shfl_xor(s1, q, 64);
+    s0 = wave_sum(s0), s1 = wave_sum(s1);
     if ((t & 63) == 0) bsum[b][t >> 6][0] = s0, bsum[b][t >> 6][1] = s1;
   }
   __syncthreads();
@@ -181,15 +152,13 @@ __global__ __launch_bounds__(kPT) void phase_kernel(PhaseParams p) {
     const double gr = (bsum[b][0][1] + bsum[b][1][1] + bsum[b][2][1] + bsum[b][3][1]) / (double)n;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     for (int k = blo[b] + t; k < bhi[b]; k += kPT) {
-      const double2 g = Z[slot(ph_brev(k, bits))];
+      const double2 g = Z[slot(brev(k, bits))];
       const double dl = g.x - gl, dr = g.y - gr;
       s0 += dl * dl;
       s1 += dr * dr;
       s2 += dl * dr;
     }
-#pragma unroll
-    for (int q = 32; q > 0; q >>= 1)
-      s0 += __shfl_xor(s0, q, 64), s1 += __shfl_xor(s1, q, 64), s2 += __shfl_xor(s2, q, 64);
+    s0 = wave_sum(s0), s1 = wave_sum(s1), s2 = wave_sum(s2);
     if ((t & 63) == 0) bcen[b][t >> 6][0] = s0, bcen[b][t >> 6][1] = s1, bcen[b][t >> 6][2] = s2;
   }
   __syncthreads();

@@ -27,9 +27,8 @@
 // bit-reversed order; decimation in time back to natural order), so a frame needs n x 16 bytes for
 // the autocorrelation's 2n-point transform and half that for the cepstrum's.
 //
-// The high-pass recurrence is weight64.hip's chunked scan: every thread runs its chunk of n / 256
-// samples from the zero state, the chunk carries are combined over the workgroup with the powers of
-// P = A^(n/256), and every thread re-runs its chunk from its true incoming state.
+// The transform pair, the block reductions and the high-pass sections' chunked scan are wg64.hpp's,
+// compiled here with the default contraction (fused multiply-adds).
 //
 // Flat tops: scipy's find_peaks takes the middle of a plateau; here a peak is a strict local maximum
 // (x[i-1] < x[i] > x[i+1]). Float data does not produce plateaus above the height thresholds; a frame
@@ -37,6 +36,7 @@
 #include <hip/hip_runtime.h>
 
 #include "params.hpp"
+#include "wg64.hpp"
 
 namespace omega {
 
@@ -45,75 +45,23 @@ namespace {
 constexpr int kPT = kPitchThreads;
 constexpr int kPeakDistance = 20;  // find_peaks(distance=20): a kept peak removes those < 20 lags away
 
-__device__ __forceinline__ double2 pt_zmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-__device__ __forceinline__ double pt_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ double pt_max(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-__device__ __forceinline__ int pt_min_i(int v, double* red) { return (int)-pt_max(-(double)v, red); }
-
-__device__ __forceinline__ int pt_brev(int i, int bits) { return (int)(__brev((unsigned)i) >> (32 - bits)); }
-
-// K-point complex FFT in place, decimation in frequency: natural order in, X[q] at a[brev(q)] out.
-// tw[q * tws] = e^{-2 pi i q / (2 K)}
-__device__ void pt_fft_dif(double2* a, int K, const double2* __restrict__ tw, int tws) {
-  for (int half = K / 2; half >= 1; half >>= 1) {
-    const int step = K / (2 * half);
-    for (int j = threadIdx.x; j < K / 2; j += kPT) {
-      const int k = j & (half - 1), i0 = (j - k) * 2 + k, i1 = i0 + half;
-      const double2 u = a[i0], v = a[i1];
-      a[i0] = make_double2(u.x + v.x, u.y + v.y);
-      a[i1] = pt_zmul(make_double2(u.x - v.x, u.y - v.y), tw[2 * k * step * tws]);
-    }
-    __syncthreads();
-  }
-}
-// the same transform, decimation in time: element q at a[brev(q)] in, natural order out
-__device__ void pt_fft_dit(double2* a, int K, const double2* __restrict__ tw, int tws) {
-  for (int half = 1; half < K; half <<= 1) {
-    const int step = K / (2 * half);
-    for (int j = threadIdx.x; j < K / 2; j += kPT) {
-      const int k = j & (half - 1), i0 = (j - k) * 2 + k, i1 = i0 + half;
-      const double2 u = a[i0], v = pt_zmul(a[i1], tw[2 * k * step * tws]);
-      a[i0] = make_double2(u.x + v.x, u.y + v.y);
-      a[i1] = make_double2(u.x - v.x, u.y - v.y);
-    }
-    __syncthreads();
-  }
-}
-
 // irfft(g(|rfft(x)|^2)) of the 2K real samples held as a[j] = x[2j] + i x[2j+1]: on return
 // a[m] = (y[2m], y[2m+1]) of the 2K-point real result y. g maps |X_q|^2 to the real, even spectrum.
 template <class G>
 __device__ void pt_real_even_roundtrip(double2* a, int K, int bits, const double2* __restrict__ tw, int tws, G g) {
-  pt_fft_dif(a, K, tw, tws);
+  fft_dif<kPT>(a, K, tw, 2 * tws);
   // X_q (q = 0..K) from the packed spectrum Z: X_q = (Z_q + conj Z_{K-q}) / 2 + e^{-2 pi i q / 2K} (Z_q - conj Z_{K-q}) / 2i.
   // With L_q = g(|X_q|^2) the packed inverse spectrum is Z'_k = (L_k + L_{K-k}) + i e^{2 pi i k / 2K} (L_k - L_{K-k}),
   // stored conjugated so that the forward transform returns conj(K ifft). Bins k and K - k read and
   // write the same two slots, so one thread does the pair.
   for (int k = threadIdx.x; k <= K / 2; k += kPT) {
     const int m = (K - k) & (K - 1);
-    const int pk = pt_brev(k, bits), pm = pt_brev(m, bits);
+    const int pk = brev(k, bits), pm = brev(m, bits);
     const double2 zk = a[pk], zm = a[pm];
     auto L = [&](double2 za, double2 zb, int q) {  // g(|X_q|^2), za = Z_q, zb = Z_{K-q}
       const double2 e = make_double2(0.5 * (za.x + zb.x), 0.5 * (za.y - zb.y));
       const double2 o = make_double2(0.5 * (za.y + zb.y), -0.5 * (za.x - zb.x));
-      const double2 ow = pt_zmul(o, tw[q * tws]);
+      const double2 ow = zmul(o, tw[q * tws]);
       const double re = e.x + ow.x, im = e.y + ow.y;
       return g(re * re + im * im);
     };
@@ -128,58 +76,12 @@ __device__ void pt_real_even_roundtrip(double2* a, int K, int bits, const double
     if (m != k) a[pm] = pack(Lm, Lk, m);
   }
   __syncthreads();
-  pt_fft_dit(a, K, tw, tws);
+  fft_dit<kPT>(a, K, tw, 2 * tws);
   const double sc = 0.5 / K;
   for (int m = threadIdx.x; m < K; m += kPT) {
     const double2 v = a[m];
     a[m] = make_double2(v.x * sc, -v.y * sc);
   }
-  __syncthreads();
-}
-
-struct PtM2 {
-  double a, b, c, d;
-};
-__device__ __forceinline__ PtM2 pt_mmul(const PtM2& x, const PtM2& y) {
-  return {x.a * y.a + x.b * y.c, x.a * y.b + x.b * y.d, x.c * y.a + x.d * y.c, x.c * y.b + x.d * y.d};
-}
-
-// scipy.signal.sosfilt's section (DF2T, zero initial state) over v[0..n) in place
-__device__ void pt_lfilter(double* v, int n, const W64Stage& q, double2* sc) {
-  const int t = threadIdx.x;
-  const int L = (n + kPT - 1) / kPT;
-  const int lo = min(t * L, n), hi = min(lo + L, n);
-  double z0 = 0.0, z1 = 0.0;
-  auto step = [&](double u) {
-    const double y = q.b0 * u + z0;
-    z0 = q.b1 * u + z1 - q.a1 * y;
-    z1 = q.b2 * u - q.a2 * y;
-    return y;
-  };
-  for (int k = lo; k < hi; ++k) step(v[k]);
-  // inclusive scan of the chunk end states, c_t = sum_j P^(t-j) e_j with P = A^L, A = [[-a1, 1], [-a2, 0]]
-  PtM2 P{1.0, 0.0, 0.0, 1.0}, Ak{-q.a1, 1.0, -q.a2, 0.0};
-  for (int e = L; e; e >>= 1) {
-    if (e & 1) P = pt_mmul(P, Ak);
-    Ak = pt_mmul(Ak, Ak);
-  }
-  double2 c = make_double2(z0, z1);
-  for (int d = 1; d < kPT; d <<= 1) {
-    sc[t] = c;
-    __syncthreads();
-    if (t >= d) {
-      const double2 o = sc[t - d];
-      c = make_double2(c.x + (P.a * o.x + P.b * o.y), c.y + (P.c * o.x + P.d * o.y));
-    }
-    __syncthreads();
-    P = pt_mmul(P, P);
-  }
-  sc[t] = c;
-  __syncthreads();
-  const double2 s = t > 0 ? sc[t - 1] : make_double2(0.0, 0.0);
-  z0 = s.x;
-  z1 = s.y;
-  for (int k = lo; k < hi; ++k) v[k] = step(v[k]);
   __syncthreads();
 }
 
@@ -213,19 +115,20 @@ __global__ __launch_bounds__(kPT) void pitch_kernel(PitchParams p) {
       buf[i] = v;
       ss += v * v;
     }
-    const double nbad = pt_sum(bad, red);
-    const double rms_in = sqrt(pt_sum(ss, red) / n);
+    const double nbad = block_sum(bad, red);
+    const double rms_in = sqrt(block_sum(ss, red) / n);
     if (t == 0) {
       o[8] = nbad > 0.0 ? 0.0 : rms_in;
       o[9] = (nbad > 0.0 ? 1.0 : 0.0) + (rms_in < 1e-6 ? 2.0 : 0.0);
     }
     __syncthreads();
     if (p.preprocess) {
-      pt_lfilter(buf, n, p.hp[0], sc);
-      pt_lfilter(buf, n, p.hp[1], sc);
+      auto section = [&](const W64Stage& q) { sos_section_scan<kPT>(buf, n, q.b0, q.b1, q.b2, q.a1, q.a2, sc); };
+      section(p.hp[0]);
+      section(p.hp[1]);
       double fs2 = 0.0;
       for (int i = t; i < n; i += kPT) fs2 += buf[i] * buf[i];
-      const double rms = sqrt(pt_sum(fs2, red) / n);
+      const double rms = sqrt(block_sum(fs2, red) / n);
       if (p.compress) {
         if (rms > 0.01 && rms > p.comp_threshold) {
           const double gain = p.comp_threshold + (rms - p.comp_threshold) * p.comp_ratio;
@@ -244,30 +147,30 @@ __global__ __launch_bounds__(kPT) void pitch_kernel(PitchParams p) {
     // c = buf[0..K): np.std, the range's maximum, the highest strict local maximum
     double s1 = 0.0;
     for (int i = t; i < K; i += kPT) s1 += buf[i];
-    const double mean = pt_sum(s1, red) / K;
+    const double mean = block_sum(s1, red) / K;
     double s2 = 0.0;
     for (int i = t; i < K; i += kPT) {
       const double d = buf[i] - mean;
       s2 += d * d;
     }
-    const double sd = sqrt(pt_sum(s2, red) / K);
+    const double sd = sqrt(block_sum(s2, red) / K);
     const int lo = p.min_period, hi = min(p.max_period, K - 1);
     double vmax = -INFINITY;
     for (int i = lo + t; i < hi; i += kPT) vmax = fmax(vmax, buf[i]);
-    vmax = pt_max(vmax, red);
+    vmax = block_max(vmax, red);
     const double hmin = vmax * 0.3;
     double best = -INFINITY;
     for (int i = lo + 1 + t; i < hi - 1; i += kPT) {
       const double v = buf[i];
       if (buf[i - 1] < v && v > buf[i + 1] && v >= hmin) best = fmax(best, v);
     }
-    best = pt_max(best, red);
+    best = block_max(best, red);
     int at = 0x7fffffff;
     for (int i = lo + 1 + t; i < hi - 1; i += kPT) {
       const double v = buf[i];
       if (buf[i - 1] < v && v > buf[i + 1] && v >= hmin && v == best) at = min(at, i);
     }
-    at = pt_min_i(at, red);
+    at = block_min_i(at, red);
     if (t == 0) {
       const bool found = hi > lo && best > -INFINITY && at < hi;
       o[2] = found ? p.fs / at : 0.0;
@@ -277,7 +180,7 @@ __global__ __launch_bounds__(kPT) void pitch_kernel(PitchParams p) {
     // :179: x - np.mean(x) in float32, zero-padded to 2n, packed two samples per complex value
     double s = 0.0;
     for (int i = t; i < n; i += kPT) s += (double)xin(i);
-    const float mean = (float)(pt_sum(s, red) / n);
+    const float mean = (float)(block_sum(s, red) / n);
     double2* a = reinterpret_cast<double2*>(buf);
     for (int j = t; j < n; j += kPT)
       a[j] = 2 * j < n ? make_double2((double)(xin(2 * j) - mean), (double)(xin(2 * j + 1) - mean)) : make_double2(0.0, 0.0);
@@ -325,7 +228,7 @@ __global__ __launch_bounds__(kPT) void pitch_kernel(PitchParams p) {
     int first = 0x7fffffff;
     for (int i = lo + t; i < hi; i += kPT)
       if (kept[i]) first = min(first, i);
-    first = pt_min_i(first, red);
+    first = block_min_i(first, red);
     if (t == 0) {
       const bool found = hi > lo && first < hi;
       o[4] = found ? p.fs / first : 0.0;
@@ -383,7 +286,7 @@ __global__ __launch_bounds__(kPT) void pitch_kernel(PitchParams p) {
       const double v = d[i];
       if (i >= 1 && v < p.yin_threshold && v < d[i - 1] && v < d[i + 1]) first = min(first, i);
     }
-    first = pt_min_i(first, red);
+    first = block_min_i(first, red);
     if (t == 0) {
       const bool found = n >= W && first < max_tau - 1;
       double pitch = 0.0, conf = 0.0;

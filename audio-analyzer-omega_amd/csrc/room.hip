@@ -29,37 +29,16 @@
 
 #include <algorithm>
 
-#include "params.hpp"
+#pragma clang fp contract(off)  // (above the project headers: wg64.hpp takes this state)
 
-#pragma clang fp contract(off)
+#include "params.hpp"
+#include "wg64.hpp"
 
 namespace omega {
 
 namespace {
 
 constexpr int kRT = kRoomThreads, kTT = kRt60Threads;
-
-// block sums of N values at once over W waves (red: W N doubles); every thread gets every sum
-template <int N, int W>
-__device__ __forceinline__ void rm_sum(double (&v)[N], double* red) {
-#pragma unroll
-  for (int n = 0; n < N; ++n)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[n] += __shfl_xor(v[n], o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int n = 0; n < N; ++n) red[(threadIdx.x >> 6) * N + n] = v[n];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int n = 0; n < N; ++n) {
-    double s = red[n];
-#pragma unroll
-    for (int w = 1; w < W; ++w) s += red[w * N + n];
-    v[n] = s;
-  }
-}
 
 // :191-239 as base + 8 harmonic (base: 0 axial_length, 1 axial_width, 2 axial_height, 3 tangential, 4 oblique)
 __device__ __forceinline__ int rm_type(double f, const double (&h)[6]) {
@@ -106,7 +85,7 @@ __global__ __launch_bounds__(kRT) void room_modes_kernel(RoomModesParams p) {
       a[1] += v;
     }
   }
-  rm_sum<2, 4>(a, red);  // (the barriers publish x and npk)
+  block_sums<2, 4>(a, red);  // (the barriers publish x and npk)
   const bool bad = a[0] > 0.0 || p.freqs_bad;
   const double mean = (bad || K == 0) ? 0.0 : a[1] / (double)K;
   double c[1] = {0.0};
@@ -114,7 +93,7 @@ __global__ __launch_bounds__(kRT) void room_modes_kernel(RoomModesParams p) {
     const double d = x[i] - mean;
     c[0] += d * d;
   }
-  rm_sum<1, 4>(c, red);
+  block_sums<1, 4>(c, red);
   const double sd = (bad || K == 0) ? 0.0 : sqrt(c[0] / (double)K);
   if (bad || mean == 0.0 || sd == 0.0) {  // (uniform) no modes: the header alone
     for (int i = t; i < kRoomRows * kRoomCols; i += kRT)
@@ -177,7 +156,7 @@ __global__ __launch_bounds__(kRT) void room_modes_kernel(RoomModesParams p) {
   }
   double m[1] = {0.0};
   for (int j = t; j < n; j += kRT) m[0] += msev[j] >= 0.0 ? 1.0 : 0.0;  // (own entries)
-  rm_sum<1, 4>(m, red);  // (the barriers publish the per-peak arrays)
+  block_sums<1, 4>(m, red);  // (the barriers publish the per-peak arrays)
   const int count = (int)m[0];
 
   for (int j = t; j < n; j += kRT) {
@@ -263,7 +242,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
   }
   const double next = __shfl_down(inc, 1, 64);
   if (lane == 0) wtot[w] = inc;
-  rm_sum<1, NW>(nf1, red);  // (the barriers publish wtot)
+  block_sums<1, NW>(nf1, red);  // (the barriers publish wtot)
   double behind = lane < 63 ? next : 0.0;
   for (int k = NW - 1; k > w; --k) behind += wtot[k];
   if (t == 0) wtot[0] = behind + cs;  // curve[0]: what thread 0's own sweeps end on
@@ -283,7 +262,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
     cnt[1] += db > -10.0 ? 1.0 : 0.0;
     cnt[2] += db > -35.0 ? 1.0 : 0.0;
   });
-  rm_sum<3, NW>(cnt, red);
+  block_sums<3, NW>(cnt, red);
   const int i5 = (int)cnt[0], i10 = (int)cnt[1], i35 = (int)cnt[2], n = i35 - i5;
   int flags = 0;
   if (i5 >= L || i35 >= L || i35 <= i5)
@@ -306,7 +285,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
     mu[0] += (double)i / p.fs;
     mu[1] += 10.0 * log10(fmax(cv, 1e-10) / den);
   });
-  rm_sum<2, NW>(mu, red);
+  block_sums<2, NW>(mu, red);
   const double mt = mu[0] / (double)n, md = mu[1] / (double)n;
   double cen[3] = {0.0, 0.0, 0.0};
   rt_sweep(p, a32, a64, lo, hi, i5, behind, [&](int i, double cv) {
@@ -316,7 +295,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
     cen[1] += dt * dd;
     cen[2] += dd * dd;
   });
-  rm_sum<3, NW>(cen, red);
+  block_sums<3, NW>(cen, red);
   const double slope = cen[1] / cen[0], icpt = md - slope * mt;
   double ssr[1] = {0.0};
   rt_sweep(p, a32, a64, lo, hi, i5, behind, [&](int i, double cv) {
@@ -324,7 +303,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
     const double r = 10.0 * log10(fmax(cv, 1e-10) / den) - (slope * ((double)i / p.fs) + icpt);
     ssr[0] += r * r;
   });
-  rm_sum<1, NW>(ssr, red);
+  block_sums<1, NW>(ssr, red);
   if (t == 0) {
     o[0] = total, o[1] = (double)i5, o[2] = (double)i10, o[3] = (double)i35;
     o[4] = slope, o[5] = icpt, o[6] = 1.0 - ssr[0] / cen[2], o[7] = slope >= 0.0 ? 8.0 : 0.0;

@@ -55,7 +55,7 @@ __device__ __forceinline__ bool td_bad(const TdetectParams& p, int64_t f, double
   const float* g = p.spec + f * p.spec_stride;
   for (int i = threadIdx.x; i < p.n_bins; i += kT)
     if (!isfinite(g[i])) bad = 1.0;
-  return block_sum_d(bad, red) > 0.0;
+  return block_sum(bad, red) > 0.0;
 }
 
 __device__ __forceinline__ void td_envelope(const TdetectParams& p, int64_t f, double2* smem, double* red) {
@@ -77,7 +77,7 @@ __device__ __forceinline__ void td_envelope(const TdetectParams& p, int64_t f, d
     for (int j = 0; j < 11; ++j) acc = fma(wt[j], env[w0 + j], acc);
     s += acc;
   }
-  s = block_sum_d(s, red);
+  s = block_sum(s, red);
   if (threadIdx.x == 0) o[1] = s / m;
 }
 
@@ -112,7 +112,7 @@ __device__ __forceinline__ void td_flux(const TdetectParams& p, int64_t f, doubl
     w[2 + q] = mag;
     s += mag;
   }
-  s = block_sum_d(s, red);
+  s = block_sum(s, red);
   if (t == 0) {
     w[1] = s;
     o[4] = s;
@@ -153,7 +153,7 @@ __device__ __forceinline__ void td_novelty(const TdetectParams& p, int64_t f, do
     w[kTdNovBins + q] = mag;
     s += mag;
   }
-  s = block_sum_d(s, red);
+  s = block_sum(s, red);
   if (t == 0) o[7] = s;
 }
 
@@ -241,7 +241,7 @@ __device__ __forceinline__ void td_hf(const TdetectParams& p, int64_t f, double2
   td_lfilter(ext, n, true, p, V4{p.zi[0] * e1, p.zi[1] * e1, p.zi[2] * e1, p.zi[3] * e1}, sc);
   double s = 0.0;
   for (int k = t; k < m; k += kT) s = fma(ext[E + k], ext[E + k], s);
-  s = block_sum_d(s, red);
+  s = block_sum(s, red);
   if (t == 0) o[8] = s;
 }
 
@@ -265,7 +265,7 @@ __device__ __forceinline__ void td_scalar(const TdetectParams& p, int64_t f, dou
   }
   for (int i = t; i < K; i += kT)
     if (!isfinite(g[i])) bad = 1.0;
-  bad = block_sum_d(bad, red);  // (the barriers publish x and ii)
+  bad = block_sum(bad, red);  // (the barriers publish x and ii)
   if (bad > 0.0) {              // (uniform)
     if (t < kTdCols && (t == 2 || t == 3 || t >= 9 || (t == 7 && !p.nov) || (t == 8 && !p.hf))) o[t] = 0.0;
     return;
@@ -281,9 +281,9 @@ __device__ __forceinline__ void td_scalar(const TdetectParams& p, int64_t f, dou
       sgn += fabs((double)((u > 0.0) - (u < 0.0)) - (double)((v > 0.0) - (v < 0.0)));
     }
   }
-  ssq = block_sum_d(ssq, red);
-  sgn = block_sum_d(sgn, red);
-  const double peak = block_max_d(mx, red);
+  ssq = block_sum(ssq, red);
+  sgn = block_sum(sgn, red);
+  const double peak = block_max(mx, red);
   for (int i = t; i < m; i += kT)
     if (fabs(x[i]) == peak) {
       atomicMin(&ii[0], i);
@@ -330,9 +330,9 @@ __device__ __forceinline__ void td_scalar(const TdetectParams& p, int64_t f, dou
       }
     }
   }
-  fsum = block_sum_d(fsum, red);
+  fsum = block_sum(fsum, red);
 #pragma unroll
-  for (int b = 0; b < 4; ++b) band[b] = block_sum_d(band[b], red);  // (the barriers publish ii[3])
+  for (int b = 0; b < 4; ++b) band[b] = block_sum(band[b], red);  // (the barriers publish ii[3])
   if (t == 0) {
     o[2] = peak;
     o[3] = ssq;
@@ -428,8 +428,8 @@ __global__ __launch_bounds__(kT) void tdetect_cross_kernel(TdetectParams p) {
       nov += ph[kTdNovBins + i] * fmin(fabs(ph[i] - target), kTdPi);
     }
   }
-  flux = block_sum_d(flux, red);
-  nov = block_sum_d(nov, red);
+  flux = block_sum(flux, red);
+  nov = block_sum(nov, red);
   if (t == 0) {
     o[0] = (double)(shape | (sp ? 0 : 8) | (p1 ? 0 : 16));
     o[5] = flux;

@@ -45,16 +45,16 @@ __device__ __forceinline__ void transient_tail(const TransientParams& p, int64_t
     mx = fmax(mx, v);
     if (n + 1 < N) sd += es[n + 1] - v;
   }
-  s1 = block_sum_d(s1, red);
-  s2 = block_sum_d(s2, red);
-  mx = block_max_d(mx, red);
-  const double dmean = block_sum_d(sd, red) / (N - 1);
+  s1 = block_sum(s1, red);
+  s2 = block_sum(s2, red);
+  mx = block_max(mx, red);
+  const double dmean = block_sum(sd, red) / (N - 1);
   double dv = 0.0;
   for (int n = threadIdx.x; n + 1 < N; n += kTrThreads) {
     const double d = (es[n + 1] - es[n]) - dmean;
     dv += d * d;
   }
-  const double thr = sqrt(block_sum_d(dv, red) / (N - 1)) * 2.0;
+  const double thr = sqrt(block_sum(dv, red) / (N - 1)) * 2.0;
   // 6) attack points: count, attack times (10 % / 90 % searches), punch
   int cnt = 0, na = 0, np_ = 0;
   double at = 0.0, pu = 0.0;
@@ -90,8 +90,8 @@ __device__ __forceinline__ void transient_tail(const TransientParams& p, int64_t
       ++np_;
     }
   }
-  const double tc = block_sum_d(cnt, red), tna = block_sum_d(na, red), tnp = block_sum_d(np_, red);
-  const double tat = block_sum_d(at, red), tpu = block_sum_d(pu, red);
+  const double tc = block_sum(cnt, red), tna = block_sum(na, red), tnp = block_sum(np_, red);
+  const double tat = block_sum(at, red), tpu = block_sum(pu, red);
   if (threadIdx.x == 0) {
     double* o = p.out + f * kTransientCols;
     o[0] = tc;

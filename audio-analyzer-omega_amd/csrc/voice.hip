@@ -27,37 +27,16 @@
 
 #include <algorithm>
 
-#include "params.hpp"
+#pragma clang fp contract(off)  // (above the project headers: wg64.hpp takes this state)
 
-#pragma clang fp contract(off)
+#include "params.hpp"
+#include "wg64.hpp"
 
 namespace omega {
 
 namespace {
 
 constexpr int kVT = kVoiceThreads, kVW = kVoiceThreads / 64;
-
-// block sums of N values at once (red: kVW N doubles); every thread gets every sum, added in a fixed order
-template <int N>
-__device__ __forceinline__ void vc_sum(double (&v)[N], double* red) {
-#pragma unroll
-  for (int n = 0; n < N; ++n)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[n] += __shfl_xor(v[n], o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int n = 0; n < N; ++n) red[(threadIdx.x >> 6) * N + n] = v[n];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int n = 0; n < N; ++n) {
-    double s = red[n];
-#pragma unroll
-    for (int w = 1; w < kVW; ++w) s += red[w * N + n];
-    v[n] = s;
-  }
-}
 
 // 1.0 where frame f's audio holds a non-finite sample (this thread's share)
 __device__ __forceinline__ double vc_audio_bad(const VoiceParams& p, int64_t f) {
@@ -90,7 +69,7 @@ __device__ __forceinline__ void voice_spectrum(const VoiceParams& p, int64_t f, 
     if (i >= vs && i < ve) a[1] += (double)v;
   }
   if (p.pitch) a[0] += vc_audio_bad(p, f);
-  vc_sum<3>(a, red);  // (the barriers publish s and first)
+  block_sums<3, kVW>(a, red);  // (the barriers publish s and first)
   const int pitch_flag = p.pitch ? 0 : 8;
   if (a[0] > 0.0) {  // (uniform) a non-finite input: the flag alone
     if (t < 14) o[t] = t == 0 ? 4.0 : 0.0;
@@ -191,7 +170,7 @@ __device__ __forceinline__ void voice_audio(const VoiceParams& p, int64_t f, uns
     for (int i = t; i < p.n_bins; i += kVT)
       if (!isfinite(g[i])) a[0] = 1.0;
   }
-  vc_sum<2>(a, red);  // (the barriers publish x)
+  block_sums<2, kVW>(a, red);  // (the barriers publish x)
   if (a[0] > 0.0) {  // (uniform)
     if (t < 3) o[14 + t] = 0.0;
     return;
