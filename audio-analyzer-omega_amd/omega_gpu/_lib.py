@@ -274,3 +274,10 @@ def check(ctx, code: int) -> None:
     if code != OK:
         msg = lib().omega_last_error(ctx).decode() if ctx else ""
         raise (UnsupportedError if code == EUNSUP else OmegaError)(code, msg)
+
+
+def check_plain(code: int, msg: str) -> None:
+    """check() for the entry points that take no context and so leave no error text: msg says what a
+    refusal means."""
+    if code != OK:
+        raise OmegaError(code, msg)

@@ -15,7 +15,8 @@ from typing import Dict
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, _is_torch
+from ._marshal import _is_torch
+from .engine import Engine
 
 CONTENT_TYPES = ("instrumental", "vocal", "bass_heavy")
 PSYCHO, FREQ_COMP, NORMALIZE, SMOOTH = 1, 2, 4, 8

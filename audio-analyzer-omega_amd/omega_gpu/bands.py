@@ -13,14 +13,9 @@ from typing import Dict, List, Tuple
 import numpy as np
 
 from . import _lib as L
-from .engine import BandTable, Engine, Resolution
+from .engine import BandTable, utility_engine
 
 logger = logging.getLogger(__name__)
-
-
-def _table_engine(sample_rate: int, device: int) -> Engine:
-    return Engine([Resolution((20, 20000), 512, 256, 1.0)], sample_rate, min(20000, sample_rate / 2), target_bins=2,
-                  frame_size=512, device=device)
 
 
 def pipeline_band_table(sample_rate=48000, num_bands=768, fft_size=4096, min_frequency=20.0,
@@ -62,7 +57,7 @@ class PipelineBands:
         self.starts, self.ends, self.freq_compensation = pipeline_band_table(sample_rate, num_bands, fft_size, **kw)
         self.band_indices = {"starts": list(self.starts), "ends": list(self.ends)}
         self.smoothing_buffer = np.zeros(num_bands, np.float32)
-        self._eng = _table_engine(sample_rate, device)
+        self._eng = utility_engine(sample_rate, device)
         self._tables: Dict[int, BandTable] = {}
 
     def _table(self, n_bins: int) -> BandTable:
@@ -107,7 +102,7 @@ class PrecomputedFrequencyMapper:
         self.frequency_points = np.zeros(num_bars)
         for i, (s, e) in enumerate(self.band_indices[:num_bars]):
             self.frequency_points[i] = ((s + e) // 2) * self.freq_bin_width
-        self._eng = _table_engine(sample_rate, device)
+        self._eng = utility_engine(sample_rate, device)
         self._tables: Dict[Tuple[int, bool], BandTable] = {}
 
     def _create_mel_band_mapping(self) -> List[Tuple[int, int]]:

@@ -31,7 +31,9 @@ from typing import Any, Callable, Dict, Optional
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from . import _marshal as M
+from ._marshal import _is_torch, _ptr
+from .engine import utility_engine
 
 ROW_HEAD = 3  # flags, bass_max, scale_factor
 FLAG_NONFINITE = 1
@@ -55,8 +57,7 @@ def bass_mapping(sample_rate):
         if not np.any((bins >= 20) & (bins <= 200)):
             return None
         raise L.UnsupportedError(code, f"basszoom: {sample_rate} Hz has more than {MAX_BINS} bins in 20..200 Hz")
-    if code != L.OK:
-        raise L.OmegaError(code, "omega_basszoom_mapping: bad sample rate")
+    L.check_plain(code, "omega_basszoom_mapping: bad sample rate")
     bars, first, per, valid = (int(v) for v in n)
     freq_ranges = [(ranges[2 * i], ranges[2 * i + 1]) for i in range(bars)]
     mapping = [list(range(first + i * per, first + min((i + 1) * per, valid))) for i in range(bars)]
@@ -66,9 +67,7 @@ def bass_mapping(sample_rate):
 class BassZoomPanel:
     def __init__(self, sample_rate: int = 48000, clock: Callable[[], float] = time.time, device: int = 0):
         self._host_init(sample_rate, clock)
-        fmax = min(20000, sample_rate / 2)
-        self._eng = Engine([Resolution((20, fmax), 512, 256, 1.0)], int(sample_rate), fmax, target_bins=2,
-                           frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
         assert L.lib().omega_basszoom_state_size() == STATE_LEN
 
     def _host_init(self, sample_rate, clock: Callable[[], float] = time.time) -> None:
@@ -135,59 +134,25 @@ class BassZoomPanel:
         an earlier call returned for the stream, or None for a new panel. Returns (rows [F, ROW_HEAD + bars], bars,
         peaks, peak_times [F, bars] each, the new state), all float64: numpy for host input, device tensors for
         device input. Nothing of this object changes; F frames in one call equal F chained calls bit for bit."""
-        lib = L.lib()
         nb = self.bass_detail_bars
-        if _is_torch(frames):
-            import torch
-            if frames.dim() != 2:
-                raise ValueError("frames must be [F, m]")
-            if frames.dtype not in (torch.float32, torch.float64):
-                frames = frames.double()
-            if frames.stride(1) != 1 or (frames.shape[0] > 1 and frames.stride(0) < 1):
-                frames = frames.contiguous()
-            F, m = frames.shape
-            self._configure(m)
-            dev = frames.device
-            times = torch.as_tensor(np.asarray(times, np.float64) if not _is_torch(times) else times,
-                                    dtype=torch.float64, device=dev).contiguous()
-            if times.numel() != F:
-                raise ValueError("times must hold one value per frame")
-            if state is not None:
-                state = torch.as_tensor(state, dtype=torch.float64, device=dev).contiguous()
-                if state.numel() != STATE_LEN:
-                    raise ValueError(f"state must hold {STATE_LEN} values")
-            rows = torch.empty((F, ROW_HEAD + nb), dtype=torch.float64, device=dev)
-            bars, peaks, ptimes = (torch.empty((F, nb), dtype=torch.float64, device=dev) for _ in range(3))
-            new = torch.empty(STATE_LEN, dtype=torch.float64, device=dev)
-            self._eng._bind_stream(frames)
-            self._eng._check(lib.omega_basszoom_features(
-                self._eng._ctx, frames.data_ptr(), frames.stride(0) if F > 1 else m,
-                int(frames.dtype == torch.float64), times.data_ptr(), F,
-                state.data_ptr() if state is not None else None, rows.data_ptr(), bars.data_ptr(), peaks.data_ptr(),
-                ptimes.data_ptr(), new.data_ptr(), L.MEM_DEVICE))
-            return rows, bars, peaks, ptimes, new
-        frames = np.asarray(frames)
-        frames = np.ascontiguousarray(frames if frames.dtype in (np.float32, np.float64) else frames.astype(np.float64))
-        if frames.ndim != 2:
-            raise ValueError("frames must be [F, m]")
+        dev = _is_torch(frames)
+        frames, frame_ptr, stride, f64 = M.rows(frames, dev, "frames must be [F, m]", audio=True)
         F, m = frames.shape
         self._configure(m)
-        times = np.ascontiguousarray(times, np.float64)
-        if times.size != F:
+        if dev:
+            import torch
+            times = torch.as_tensor(np.asarray(times, np.float64) if not _is_torch(times) else times,
+                                    dtype=torch.float64, device=frames.device).contiguous()
+        else:
+            times = np.ascontiguousarray(times, np.float64)
+        if (times.numel() if dev else times.size) != F:
             raise ValueError("times must hold one value per frame")
-        if state is not None:
-            if _is_torch(state):
-                state = state.detach().cpu().numpy()
-            state = np.ascontiguousarray(state, np.float64)
-            if state.size != STATE_LEN:
-                raise ValueError(f"state must hold {STATE_LEN} values")
-        rows = np.empty((F, ROW_HEAD + nb), np.float64)
-        bars, peaks, ptimes = (np.empty((F, nb), np.float64) for _ in range(3))
-        new = np.empty(STATE_LEN, np.float64)
-        self._eng._check(lib.omega_basszoom_features(
-            self._eng._ctx, frames.ctypes.data, m, int(frames.dtype == np.float64), times.ctypes.data, F,
-            state.ctypes.data if state is not None else None, rows.ctypes.data, bars.ctypes.data, peaks.ctypes.data,
-            ptimes.ctypes.data, new.ctypes.data, L.MEM_HOST))
+        state = M.state_blob(state, frames, STATE_LEN)
+        rows = M.alloc(frames, (F, ROW_HEAD + nb), np.float64)
+        bars, peaks, ptimes = (M.alloc(frames, (F, nb), np.float64) for _ in range(3))
+        new = M.alloc(frames, (STATE_LEN,), np.float64)
+        M.call(self._eng, L.lib().omega_basszoom_features, frames, frame_ptr, stride, f64, _ptr(times), F,
+               _ptr(state), _ptr(rows), _ptr(bars), _ptr(peaks), _ptr(ptimes), _ptr(new))
         return rows, bars, peaks, ptimes, new
 
     # -- the host part --

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .engine import Engine, Resolution
+from .engine import utility_engine
 
 
 class FFTRequest:
@@ -35,8 +35,7 @@ class BatchedFFTProcessor:
         self.common_fft_sizes = [512, 1024, 2048, 4096, 8192, 16384]
         self.batch_times = []
         self.last_batch_size = 0
-        self._eng = Engine([Resolution((20, 20000), 512, 256, 1.0)], 48000, 20000, target_bins=2, frame_size=512,
-                           device=device)
+        self._eng = utility_engine(48000, device)  # (the FFTs read no sample rate)
         self._seq = 0
 
     def prepare_batch(self, panel_id: str, audio_data: np.ndarray, fft_size: int, window_type: str = "hann") -> str:

@@ -17,7 +17,7 @@ from collections import Counter, deque
 
 import numpy as np
 
-from .engine import Engine, Resolution
+from .engine import utility_engine
 
 _BLEND = {"metal": 0.7, "rock": 0.7, "jazz": 0.5}
 _E2 = 82.41  # chromagram.py:592-599: E2 and the drop tunings' lowest-string references
@@ -33,8 +33,7 @@ class ChromagramAnalyzer:
         self.chroma_history = deque(maxlen=8)
         self.current_genre = "pop"
         self.tuning_history = []
-        self._eng = Engine([Resolution((20, 20000), 512, 256, 1.0)], sample_rate, min(20000, sample_rate / 2),
-                           target_bins=2, frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
 
     def _raw(self, spectra: np.ndarray, freqs: np.ndarray) -> np.ndarray:
         spectra = np.atleast_2d(spectra)

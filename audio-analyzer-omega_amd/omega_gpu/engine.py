@@ -11,6 +11,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib as L
+from ._marshal import _is_torch, _ptr, alloc, call
 
 
 @dataclass(frozen=True)
@@ -37,18 +38,6 @@ NORTHSTAR_RESOLUTIONS = (  # BASELINE.json north-star sizes, same ranges/weights
     Resolution((5000, 20000), 1024, 256, 1.5),
 )
 METER_KEYS = ("momentary", "short_term", "integrated", "range", "true_peak")
-
-
-def _is_torch(a) -> bool:
-    return hasattr(a, "data_ptr") and hasattr(a, "is_cuda")
-
-
-def _ptr(a) -> Optional[int]:
-    if a is None:
-        return None
-    if _is_torch(a):
-        return a.data_ptr()
-    return a.ctypes.data
 
 
 class Engine:
@@ -158,14 +147,6 @@ class Engine:
         self._check(L.lib().omega_flush_meters(self._ctx))
         self._held = None
 
-    # -- helpers --
-    def _alloc(self, like, shape, dtype):
-        if _is_torch(like):
-            import torch
-            tdt = {np.float32: torch.float32, np.float64: torch.float64}[dtype]
-            return torch.empty(shape, dtype=tdt, device=like.device)
-        return np.empty(shape, dtype=dtype)
-
     # -- the fused per-channel-frame path --
     def process_stream(self, x, n_samples: int, hop: int, channel_stride: int = 0, **kw) -> Dict:
         """Stream layout (omega_process_stream): one frame per `hop` samples once W samples have
@@ -184,19 +165,19 @@ class Engine:
         ncf = n_frames * self.C
         o = dict(out or {})
         if combined and "combined" not in o:
-            o["combined"] = self._alloc(x, (ncf, self.T), np.float32)
+            o["combined"] = alloc(x, (ncf, self.T), np.float32)
         if lufs and "lufs_inst" not in o:
-            o["lufs_inst"] = self._alloc(x, (ncf,), np.float32)
+            o["lufs_inst"] = alloc(x, (ncf,), np.float32)
         if true_peak and "true_peak_db" not in o:
-            o["true_peak_db"] = self._alloc(x, (ncf,), np.float32)
+            o["true_peak_db"] = alloc(x, (ncf,), np.float32)
         if meters and "meters" not in o:
-            o["meters"] = self._alloc(x, (ncf, L.N_METERS), np.float64)
+            o["meters"] = alloc(x, (ncf, L.N_METERS), np.float64)
         if weighted and "weighted" not in o:
-            o["weighted"] = self._alloc(x, (ncf, self.W), np.float32)
+            o["weighted"] = alloc(x, (ncf, self.W), np.float32)
         if mags:
             sel = range(len(self.resolutions)) if mags is True else mags
             for r in sel:
-                o.setdefault(f"mag{r}", self._alloc(x, (ncf, self.resolutions[r].fft_size // 2 + 1), np.float32))
+                o.setdefault(f"mag{r}", alloc(x, (ncf, self.resolutions[r].fft_size // 2 + 1), np.float32))
         outs = L.Outputs()
         outs.combined = _ptr(o.get("combined"))
         outs.lufs_inst = _ptr(o.get("lufs_inst"))
@@ -271,18 +252,15 @@ class Engine:
             li, tp = lufs_inst.contiguous(), tp_db.contiguous()
             if li.dtype != torch.float32 or tp.dtype != torch.float32:
                 raise ValueError("load_meter_history: float32 rows")
-            if li.numel():
-                self._bind_stream(li)
-            mem = L.MEM_DEVICE
         else:
             li = np.ascontiguousarray(lufs_inst, dtype=np.float32)
             tp = np.ascontiguousarray(tp_db, dtype=np.float32)
-            mem = L.MEM_HOST
         n_l, n_t = li.shape[0] if li.ndim else 0, tp.shape[0] if tp.ndim else 0
         if li.ndim != 2 or li.shape[1] != self.C or (n_t and (tp.ndim != 2 or tp.shape[1] != self.C)):
             raise ValueError(f"load_meter_history: [n, {self.C}] rows")
-        self._check(L.lib().omega_meter_load_history(self._ctx, _ptr(li) if n_l else None, int(n_l),
-                                                     _ptr(tp) if n_t else None, int(n_t), mem))
+        # (an empty history reads no device memory: the stream stays as it was)
+        call(self, L.lib().omega_meter_load_history, li, _ptr(li) if n_l else None, int(n_l),
+             _ptr(tp) if n_t else None, int(n_t), bind=n_l > 0)
         self._held = None  # (the load ran a pending meter segment first)
 
     def meter_update(self, lufs_inst, tp_db, n_frames: int):
@@ -294,16 +272,11 @@ class Engine:
             if li.dtype != torch.float32 or tp.dtype != torch.float32 or li.numel() != n_frames * self.C \
                     or tp.numel() != n_frames * self.C:
                 raise ValueError(f"meter_update: float32 values for {n_frames} x {self.C} channel-frames")
-            self._bind_stream(li)
-            out = torch.empty((n_frames * self.C, L.N_METERS), dtype=torch.float64, device=li.device)
-            self._check(L.lib().omega_meter_update(self._ctx, _ptr(li), _ptr(tp), int(n_frames), _ptr(out),
-                                                   L.MEM_DEVICE))
-            return out
-        li = np.ascontiguousarray(lufs_inst, dtype=np.float32)
-        tp = np.ascontiguousarray(tp_db, dtype=np.float32)
-        out = np.empty((n_frames * self.C, L.N_METERS), np.float64)
-        self._check(L.lib().omega_meter_update(self._ctx, li.ctypes.data, tp.ctypes.data, int(n_frames),
-                                               out.ctypes.data, L.MEM_HOST))
+        else:
+            li = np.ascontiguousarray(lufs_inst, dtype=np.float32)
+            tp = np.ascontiguousarray(tp_db, dtype=np.float32)
+        out = alloc(li, (n_frames * self.C, L.N_METERS), np.float64)
+        call(self, L.lib().omega_meter_update, li, _ptr(li), _ptr(tp), int(n_frames), _ptr(out))
         return out
 
     def calculate_lufs(self, x: np.ndarray, mode: str = "K", oversampling: int = 4):
@@ -340,11 +313,11 @@ class Engine:
         n, m = x.shape
         o = dict(out or {})
         if bands is not None and "bands" not in o:
-            o["bands"] = self._alloc(x, (n, bands.n_out), np.float32)
+            o["bands"] = alloc(x, (n, bands.n_out), np.float32)
         if chroma and "chroma" not in o:
-            o["chroma"] = self._alloc(x, (n, 12), np.float64)
+            o["chroma"] = alloc(x, (n, 12), np.float64)
         if mags and "mag" not in o:
-            o["mag"] = self._alloc(x, (n, m // 2 + 1), np.float32)
+            o["mag"] = alloc(x, (n, m // 2 + 1), np.float32)
         if dev:
             self._bind_stream(x)
         self._check(L.lib().omega_spectra(self._ctx, _ptr(x), n, m, L.WIN.get(window, 1),
@@ -361,7 +334,7 @@ class Engine:
         if not dev:
             mags = np.ascontiguousarray(mags, dtype=np.float32)
         F, n = mags.shape
-        o = out if out is not None else self._alloc(mags, (F, 14), np.float64)
+        o = out if out is not None else alloc(mags, (F, 14), np.float64)
         if dev:
             self._bind_stream(mags)
         self._check(L.lib().omega_drum_features(self._ctx, _ptr(mags), int(F), int(n), int(mags.stride(0) if dev else n),
@@ -377,6 +350,17 @@ class Engine:
         self._check(L.lib().omega_chroma(self._ctx, s.ctypes.data, s.shape[0], s.shape[1], float(df),
                                          out.ctypes.data, L.MEM_HOST))
         return out
+
+
+def utility_engine(sample_rate, device: int = 0, n_channels: int = 1) -> Engine:
+    """A context and its stream for the entry points that never read the multi-resolution tables: the
+    feature panels, the meters, the band tables, the plain FFTs. omega_create wants at least one
+    resolution, so this one is a placeholder: its range feeds only the weight and combine tables of
+    process_frames / combine, which no owner of a utility engine calls. (20, 20000) under
+    max_freq = min(20000, fs / 2) is accepted at every positive rate."""
+    sample_rate = int(sample_rate)
+    return Engine([Resolution((20, 20000), 512, 256, 1.0)], sample_rate, min(20000, sample_rate / 2),
+                  target_bins=2, frame_size=512, n_channels=n_channels, device=device)
 
 
 class BandTable:

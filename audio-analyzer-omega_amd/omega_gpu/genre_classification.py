@@ -32,7 +32,8 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from ._marshal import _is_torch
+from .engine import utility_engine
 
 COLUMNS = ("spectral_centroid", "spectral_rolloff", "rolloff_index", "zero_crossings", "spectral_bandwidth",
            "dynamic_range", "loud", "quiet", "rms", "spectral_complexity", "bass_emphasis", "vocal_presence",
@@ -49,8 +50,7 @@ class GenreClassifier:
         if not sample_rate > 0:
             raise ValueError("Sample rate must be positive")
         self._host_init(sample_rate, genre_patterns)
-        self._eng = Engine([Resolution((20, min(20000, sample_rate / 2)), 512, 256, 1.0)], sample_rate,
-                           min(20000, sample_rate / 2), target_bins=2, frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
 
     def _host_init(self, sample_rate, genre_patterns=None) -> None:
         """The state that needs no device (the tests build the host logic on it alone)."""

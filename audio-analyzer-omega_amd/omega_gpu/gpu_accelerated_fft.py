@@ -18,7 +18,6 @@ get the first one's spectrum, as in the reference. Every length runs on the devi
 """
 from __future__ import annotations
 
-import ctypes as C
 import logging
 import threading
 from typing import Any, Dict, Optional, Tuple
@@ -26,7 +25,8 @@ from typing import Any, Dict, Optional, Tuple
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from ._marshal import _is_torch
+from .engine import utility_engine
 
 logger = logging.getLogger(__name__)
 _SIZES = (512, 1024, 2048, 4096, 8192, 16384)
@@ -43,8 +43,7 @@ class GPUAcceleratedFFT:
         self.fft_cache: Dict[tuple, Dict[str, Any]] = {}
         self.cache_lock = threading.Lock()
         self.device = device
-        self._eng = Engine([Resolution((20, 20000), 512, 256, 1.0)], 48000, 20000, target_bins=2, frame_size=512,
-                           device=device)
+        self._eng = utility_engine(48000, device)  # (the FFTs read no sample rate)
         self.windows = {name: {n: fn(n).astype(np.float32) for n in _SIZES}
                         for name, fn in (("hann", np.hanning), ("hamming", np.hamming), ("blackman", np.blackman))}
 

@@ -7,7 +7,9 @@ shape, HNR and the LPC formants per frame -- over libomega.so's omega_harmonic_a
 numpy or device torch); ``detect_harmonic_series(fft_data, freqs, audio_data)`` returns the reference's
 dict for one frame, the per-series ``harmonics`` lists rebuilt on the host from the device's bins. The
 previous spectrum the flux compares with lives in the context (``reset()`` forgets it); the two
-60-deep histories are kept here.
+60-deep histories are kept here. Device batches follow the facades' common row rule (_marshal.rows): rows
+that overlap or belong to a wider table are read in place; a batch with ``stride(0) < 1`` and F > 1 (an
+``expand`` of one row) is copied and analysed, where this facade once left it to the library to refuse.
 
 Instrument identification (:335-431) is scalar host work on at most three series. The profile table is
 data the caller supplies (``HarmonicAnalyzer(fs, instrument_profiles=reference.instrument_profiles)``);
@@ -27,7 +29,9 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from . import _marshal as M
+from ._marshal import _is_torch, _ptr
+from .engine import utility_engine
 
 COLUMNS = ("series_count", "dominant_fundamental", "thd", "thd_plus_noise", "spectral_centroid", "spectral_spread",
            "spectral_flux", "spectral_rolloff", "inharmonicity", "hnr_db", "formant_count", "F1", "F2", "F3", "F4",
@@ -62,8 +66,7 @@ class HarmonicAnalyzer:
         self.spectral_centroid_history = deque(maxlen=60)
         self.thd_history = deque(maxlen=60)
         self.metrics = HarmonicMetrics(sample_rate, device=device)
-        self._eng = Engine([Resolution((20, min(20000, sample_rate / 2)), 512, 256, 1.0)], sample_rate,
-                           min(20000, sample_rate / 2), target_bins=2, frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
         self._freqs: Optional[np.ndarray] = None
 
     # -- the device part --
@@ -90,54 +93,22 @@ class HarmonicAnalyzer:
         stream in order: the flux of frame f compares with frame f-1, that of frame 0 with the last frame of
         the previous call."""
         dev = _is_torch(spectra)
-        lib = L.lib()
-        if dev:
-            import torch
-            if frames is not None and not _is_torch(frames):
-                raise ValueError("spectra and frames must both be device tensors or both host arrays")
-            if spectra.dtype != torch.float32:
-                spectra = spectra.float()
-            if spectra.dim() != 2:
-                raise ValueError("spectra must be [F, K]")
-            if spectra.stride(1) != 1:
-                spectra = spectra.contiguous()
-            F, K = spectra.shape
-            self._configure(freqs, K)
-            ap, f64, m, astride = None, 0, 0, 1
-            if frames is not None:
-                if frames.dtype not in (torch.float32, torch.float64):
-                    frames = frames.double()
-                if frames.dim() != 2 or frames.shape[0] != F:
-                    raise ValueError("frames must be [F, m]")
-                if frames.stride(1) != 1:
-                    frames = frames.contiguous()
-                ap, f64, m = frames.data_ptr(), int(frames.dtype == torch.float64), frames.shape[1]
-                astride = frames.stride(0) if F > 1 else m
-            out = torch.empty((F, len(COLUMNS)), dtype=torch.float64, device=spectra.device)
-            sb = torch.empty((F, self.max_series, SERIES_COLS), dtype=torch.int32, device=spectra.device)
-            ss = torch.empty((F, self.max_series), dtype=torch.float64, device=spectra.device)
-            self._eng._bind_stream(spectra)
-            self._eng._check(lib.omega_harmonic_analyze(self._eng._ctx, spectra.data_ptr(), spectra.stride(0) if F > 1 else K,
-                                                        ap, f64, m, astride, F, out.data_ptr(), sb.data_ptr(),
-                                                        ss.data_ptr(), L.MEM_DEVICE))
-            return out, sb, ss
-        spectra = np.ascontiguousarray(spectra, np.float32)
-        if spectra.ndim != 2:
-            raise ValueError("spectra must be [F, K]")
+        if dev and frames is not None and not _is_torch(frames):
+            raise ValueError(M.MIXED_SIDES)
+        spectra, spec_ptr, spec_stride, _ = M.rows(spectra, dev, "spectra must be [F, K]")
         F, K = spectra.shape
         self._configure(freqs, K)
-        ap, f64, m = None, 0, 0
+        audio_ptr, f64, m, audio_stride = None, 0, 0, 1  # (no audio: a null pointer, and any positive stride)
         if frames is not None:
-            frames = np.asarray(frames)
-            frames = np.ascontiguousarray(frames if frames.dtype in (np.float32, np.float64) else frames.astype(np.float64))
-            if frames.ndim != 2 or frames.shape[0] != F:
+            frames, audio_ptr, audio_stride, f64 = M.rows(frames, dev, "frames must be [F, m]", audio=True)
+            if frames.shape[0] != F:
                 raise ValueError("frames must be [F, m]")
-            ap, f64, m = frames.ctypes.data, int(frames.dtype == np.float64), frames.shape[1]
-        out = np.empty((F, len(COLUMNS)), np.float64)
-        sb = np.empty((F, self.max_series, SERIES_COLS), np.int32)
-        ss = np.empty((F, self.max_series), np.float64)
-        self._eng._check(lib.omega_harmonic_analyze(self._eng._ctx, spectra.ctypes.data, K, ap, f64, m, max(m, 1), F,
-                                                    out.ctypes.data, sb.ctypes.data, ss.ctypes.data, L.MEM_HOST))
+            m = frames.shape[1]
+        out = M.alloc(spectra, (F, len(COLUMNS)), np.float64)
+        sb = M.alloc(spectra, (F, self.max_series, SERIES_COLS), np.int32)
+        ss = M.alloc(spectra, (F, self.max_series), np.float64)
+        M.call(self._eng, L.lib().omega_harmonic_analyze, spectra, spec_ptr, spec_stride, audio_ptr, f64, m,
+               audio_stride, F, _ptr(out), _ptr(sb), _ptr(ss))
         return out, sb, ss
 
     # -- the reference's surface --

@@ -36,7 +36,8 @@ from typing import Any, Dict, Optional
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from ._marshal import _is_torch
+from .engine import utility_engine
 
 COLUMNS = ("rms", "sub_bass_presence", "kick_peak_count", "kick_pattern_factor", "hihat_zero_crossings",
            "hihat_density", "spectral_tilt", "vocal_peak_count", "vocal_presence", "flags", "sub_bass_rms",
@@ -54,8 +55,7 @@ class HipHopDetector:
         if not sample_rate > 0:
             raise ValueError("Sample rate must be positive")
         self._host_init(sample_rate)
-        self._eng = Engine([Resolution((20, min(20000, sample_rate / 2)), 512, 256, 1.0)], sample_rate,
-                           min(20000, sample_rate / 2), target_bins=2, frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
 
     def _host_init(self, sample_rate) -> None:
         """The state that needs no device (the tests build the host logic on it alone)."""

@@ -33,7 +33,9 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from . import _marshal as M
+from ._marshal import _is_torch, _ptr
+from .engine import utility_engine
 
 logger = logging.getLogger(__name__)
 
@@ -50,8 +52,7 @@ class PhaseCorrelation:
         if not sample_rate > 0:
             raise ValueError("Sample rate must be positive")
         self._host_init(sample_rate, frame_size)
-        self._eng = Engine([Resolution((20, min(20000, sample_rate / 2)), 512, 256, 1.0)], sample_rate,
-                           min(20000, sample_rate / 2), target_bins=2, frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
 
     def _host_init(self, sample_rate, frame_size: int = 2048) -> None:
         """The state that needs no device (the tests drive the host logic on it alone)."""
@@ -85,41 +86,35 @@ class PhaseCorrelation:
     def analyze_frames(self, left, right):
         """left, right [F, m] float32 / float64: host numpy, or device torch tensors whose rows may overlap and
         share one row stride (the two halves of a planar [F, 2, m] batch). Returns (rows [F, len(COLUMNS)],
-        points [F, 128, 2]) float64, numpy for host input and device tensors for device input. No state."""
-        lib = L.lib()
-        if _is_torch(left):
-            import torch
-            if not _is_torch(right) or left.shape != right.shape or left.dim() != 2:
-                raise ValueError("left and right must both be [F, m] device tensors")
-            if left.dtype not in (torch.float32, torch.float64):
-                left = left.double()
-            right = right.to(left.dtype)
-            F, m = left.shape
-            ok = lambda x: x.stride(1) == 1 and (F == 1 or x.stride(0) >= 1)  # noqa: E731
-            if not (ok(left) and ok(right) and (F == 1 or left.stride(0) == right.stride(0))):
-                left, right = left.contiguous(), right.contiguous()
-            self._configure(m)
-            rows = torch.empty((F, len(COLUMNS)), dtype=torch.float64, device=left.device)
-            pts = torch.empty((F, N_POINTS, 2), dtype=torch.float64, device=left.device)
-            if F:
-                self._eng._bind_stream(left)
-                self._eng._check(lib.omega_phase_correlation(
-                    self._eng._ctx, left.data_ptr(), right.data_ptr(), int(left.dtype == torch.float64),
-                    left.stride(0) if F > 1 else m, F, rows.data_ptr(), pts.data_ptr(), L.MEM_DEVICE))
-            return rows, pts
-        left, right = np.asarray(left), np.asarray(right)
-        dt = np.float32 if left.dtype == np.float32 and right.dtype == np.float32 else np.float64
-        left, right = np.ascontiguousarray(left, dt), np.ascontiguousarray(right, dt)
-        if left.ndim != 2 or left.shape != right.shape:
-            raise ValueError("left and right must both be [F, m]")
+        points [F, 128, 2]) float64, numpy for host input and device tensors for device input. No state.
+        A device operand is copied when its own layout needs it (_marshal.rows); when the two row strides then
+        differ, both are copied. (An operand that is usable in place is no longer copied merely because the
+        other one was, as long as the strides agree.)"""
+        dev = _is_torch(left)
+        if dev:
+            message = "left and right must both be [F, m] device tensors"
+            if not _is_torch(right) or left.shape != right.shape:
+                raise ValueError(message)
+            left, _, stride, f64 = M.rows(left, True, message, audio=True)
+            right, _, right_stride, _ = M.rows(right.to(left.dtype), True, message, audio=True)
+            if left.shape[0] > 1 and stride != right_stride:  # (one row stride serves both, or both are copied)
+                left, right, stride = left.contiguous(), right.contiguous(), left.shape[1]
+        else:
+            message = "left and right must both be [F, m]"
+            left, right = np.asarray(left), np.asarray(right)
+            if left.dtype != np.float32 or right.dtype != np.float32:
+                left, right = np.asarray(left, np.float64), np.asarray(right, np.float64)
+            left, _, stride, f64 = M.rows(left, False, message, audio=True)
+            right = M.rows(right, False, message, audio=True)[0]
+            if left.shape != right.shape:
+                raise ValueError(message)
         F, m = left.shape
         self._configure(m)
-        rows = np.empty((F, len(COLUMNS)), np.float64)
-        pts = np.empty((F, N_POINTS, 2), np.float64)
+        rows = M.alloc(left, (F, len(COLUMNS)), np.float64)
+        pts = M.alloc(left, (F, N_POINTS, 2), np.float64)
         if F:
-            self._eng._check(lib.omega_phase_correlation(self._eng._ctx, left.ctypes.data, right.ctypes.data,
-                                                         int(dt == np.float64), m, F, rows.ctypes.data,
-                                                         pts.ctypes.data, L.MEM_HOST))
+            M.call(self._eng, L.lib().omega_phase_correlation, left, _ptr(left), _ptr(right), f64, stride, F,
+                   _ptr(rows), _ptr(pts))
         return rows, pts
 
     # -- the reference's surface --

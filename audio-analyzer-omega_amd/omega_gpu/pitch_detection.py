@@ -5,7 +5,10 @@ by confidence -- over libomega.so's omega_pitch_detect, with the reference's con
 
 ``detect_batch(frames)`` analyses a batch of one stream's frames in one launch and advances the
 histories in order; ``detect_pitch_advanced(_safe)(signal)`` return the reference's dicts. The note
-name, the stability score and the two histories (:435-483) are scalar float64 work on the host.
+name, the stability score and the two histories (:435-483) are scalar float64 work on the host. Device
+batches follow the facades' common row rule (_marshal.rows): overlapping rows are read in place; a batch
+with ``stride(0) < 1`` and F > 1 (an ``expand`` of one frame) is copied and analysed, where this facade once
+left it to the library to refuse; samples that are neither float32 nor float64 become float64.
 
 The combination follows the reference, not the configuration: the acceptance thresholds 0.15 / 0.2 /
 0.25 and the weights 0.8 / 0.9 / 1.1 are hard-coded in combine_pitch_estimates (:384-393), and the
@@ -26,7 +29,9 @@ from typing import Any, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from . import _marshal as M
+from ._marshal import _is_torch, _ptr
+from .engine import utility_engine
 
 logger = logging.getLogger(__name__)
 COLUMNS = ("pitch", "confidence", "cepstral_pitch", "cepstral_confidence", "autocorr_pitch", "autocorr_confidence",
@@ -158,8 +163,7 @@ class CepstralAnalyzer:
         self.processing_times = deque(maxlen=100) if self.config.enable_performance_monitoring else None
         self.error_count = 0
         self.last_error_time = 0
-        self._eng = Engine([Resolution((20, 20000), 512, 256, 1.0)], sample_rate, min(20000, sample_rate / 2),
-                           target_bins=2, frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
         c = self.config
         cfg = L.PitchConfig(int(sample_rate), float(c.min_pitch), float(c.max_pitch), float(c.yin_threshold),
                             int(c.yin_window_size), int(bool(c.enable_preprocessing)), float(c.highpass_frequency),
@@ -170,28 +174,11 @@ class CepstralAnalyzer:
     # -- the device part --
     def _detect(self, frames):
         """frames [F, n] -> ([F, 10] host float64, the block as returned to detect_batch's caller)."""
-        dev = _is_torch(frames)
-        if not dev:
-            frames = np.asarray(frames)
-            frames = np.ascontiguousarray(frames if frames.dtype in (np.float32, np.float64) else frames.astype(np.float64))
-        if frames.ndim != 2:
-            raise ValueError("frames must be [F, n]")
+        frames, frame_ptr, stride, f64 = M.rows(frames, _is_torch(frames), "frames must be [F, n]", audio=True)
         F, n = frames.shape
-        f64 = 1 if str(frames.dtype).endswith("float64") else 0
-        lib = L.lib()
-        if dev:
-            import torch
-            if frames.stride(1) != 1:
-                frames = frames.contiguous()
-            out = torch.empty((F, len(COLUMNS)), dtype=torch.float64, device=frames.device)
-            self._eng._bind_stream(frames)
-            self._eng._check(lib.omega_pitch_detect(self._eng._ctx, frames.data_ptr(), f64, F, n,
-                                                    frames.stride(0) if F > 1 else n, out.data_ptr(), L.MEM_DEVICE))
-            return out.cpu().numpy(), out
-        out = np.empty((F, len(COLUMNS)), np.float64)
-        self._eng._check(lib.omega_pitch_detect(self._eng._ctx, frames.ctypes.data, f64, F, n, n, out.ctypes.data,
-                                                L.MEM_HOST))
-        return out, out
+        out = M.alloc(frames, (F, len(COLUMNS)), np.float64)
+        M.call(self._eng, L.lib().omega_pitch_detect, frames, frame_ptr, f64, F, n, stride, _ptr(out))
+        return (out.cpu().numpy() if _is_torch(out) else out), out
 
     def detect_batch(self, frames):
         """frames [F, n] (float32 / float64; host numpy, or device torch -- rows may overlap, e.g. an

@@ -21,7 +21,7 @@ from typing import Dict
 
 import numpy as np
 
-from .engine import Engine, Resolution
+from .engine import utility_engine
 
 logger = logging.getLogger(__name__)
 
@@ -57,8 +57,7 @@ class ProfessionalMetering:
         self.a_weighting_filter = self.create_a_weighting_filter()
         self.c_weighting_filter = self.create_c_weighting_filter()
         # one context: its meter state is the four deques of :20-25 for one stream
-        self._eng = Engine([Resolution((20, 20000), 512, 256, 1.0)], sample_rate, min(20000, sample_rate / 2),
-                           target_bins=2, frame_size=512, n_channels=1, device=device)
+        self._eng = utility_engine(sample_rate, device)
 
     @staticmethod
     def _frame(audio_data):

@@ -38,7 +38,9 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from . import _marshal as M
+from ._marshal import _is_torch, _ptr
+from .engine import utility_engine
 
 logger = logging.getLogger(__name__)
 
@@ -97,9 +99,7 @@ class RoomModeConfig:
 class RoomModeAnalyzer:
     def __init__(self, sample_rate: int = 48000, config: Optional[RoomModeConfig] = None, device: int = 0):
         self._host_init(sample_rate, config)
-        top = min(20000, sample_rate / 2)
-        self._eng = Engine([Resolution((20, top), 512, 256, 1.0)], int(sample_rate), top, target_bins=2,
-                           frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
 
     def _host_init(self, sample_rate: int = 48000, config: Optional[RoomModeConfig] = None) -> None:
         """The state that needs no device (the tests drive the host methods on it alone)."""
@@ -218,37 +218,19 @@ class RoomModeAnalyzer:
         """spectra [F, n_bins] float32 / float64 (host numpy, or a device torch tensor whose rows may overlap),
         freqs [n_bins] strictly increasing. Returns the raw rows [F, 65, 8] float64 (row 0 the header count,
         flags, mean, std; then MODE_COLUMNS), numpy for host input and a device tensor for device input."""
-        lib = L.lib()
         freqs = np.ascontiguousarray(np.asarray(freqs.cpu() if _is_torch(freqs) else freqs), np.float64)
-        if _is_torch(spectra):
-            import torch
-            if spectra.dim() != 2 or spectra.shape[1] != len(freqs):
-                raise ValueError("spectra must be [F, len(freqs)]")
-            if spectra.dtype not in (torch.float32, torch.float64):
-                spectra = spectra.double()
-            F, nb = spectra.shape
-            if not (spectra.stride(1) == 1 and (F == 1 or spectra.stride(0) >= 1)):
-                spectra = spectra.contiguous()
-            self._configure(freqs)
-            out = torch.empty((F, ROWS, COLS), dtype=torch.float64, device=spectra.device)
-            if F:
-                self._eng._bind_stream(spectra)
-                self._eng._check(lib.omega_room_modes(self._eng._ctx, spectra.data_ptr(),
-                                                      int(spectra.dtype == torch.float64),
-                                                      spectra.stride(0) if F > 1 else nb, F, out.data_ptr(),
-                                                      L.MEM_DEVICE))
-            return out
-        spectra = np.asarray(spectra)
-        dt = np.float32 if spectra.dtype == np.float32 else np.float64
-        spectra = np.ascontiguousarray(spectra, dt)
-        if spectra.ndim != 2 or spectra.shape[1] != len(freqs):
-            raise ValueError("spectra must be [F, len(freqs)]")
+        message = "spectra must be [F, len(freqs)]"
+        dev = _is_torch(spectra)
+        if dev and (spectra.dim() != 2 or spectra.shape[1] != len(freqs)):  # (refused before any copy)
+            raise ValueError(message)
+        spectra, spec_ptr, stride, f64 = M.rows(spectra, dev, message, audio=True)
         F, nb = spectra.shape
+        if nb != len(freqs):
+            raise ValueError(message)
         self._configure(freqs)
-        out = np.empty((F, ROWS, COLS), np.float64)
+        out = M.alloc(spectra, (F, ROWS, COLS), np.float64)
         if F:
-            self._eng._check(lib.omega_room_modes(self._eng._ctx, spectra.ctypes.data, int(dt == np.float64), nb, F,
-                                                  out.ctypes.data, L.MEM_HOST))
+            M.call(self._eng, L.lib().omega_room_modes, spectra, spec_ptr, f64, stride, F, _ptr(out))
         return out
 
     @staticmethod
@@ -285,38 +267,15 @@ class RoomModeAnalyzer:
     def analyze_histories(self, audio, frame_len: int = 0):
         """audio [S, L] float32 / float64 (host numpy, or a device torch tensor whose rows may overlap). Returns
         (rows [S, 8] in RT60_COLUMNS order, energies [S, L / frame_len] or None), float64."""
-        lib = L.lib()
         W = int(frame_len)
         if self._configured is None:  # (the decay fit reads the sample rate alone)
             self._configure(np.linspace(0.0, self.sample_rate / 2, 512))
-        if _is_torch(audio):
-            import torch
-            if audio.dim() != 2:
-                raise ValueError("audio must be [S, L]")
-            if audio.dtype not in (torch.float32, torch.float64):
-                audio = audio.double()
-            S, n = audio.shape
-            if not (audio.stride(1) == 1 and (S == 1 or audio.stride(0) >= 1)):
-                audio = audio.contiguous()
-            rows = torch.empty((S, RT60_COLS), dtype=torch.float64, device=audio.device)
-            en = torch.empty((S, n // W), dtype=torch.float64, device=audio.device) if W else None
-            if S:
-                self._eng._bind_stream(audio)
-                self._eng._check(lib.omega_room_decay(self._eng._ctx, audio.data_ptr(), int(audio.dtype == torch.float64),
-                                                     audio.stride(0) if S > 1 else n, n, W, S, rows.data_ptr(),
-                                                     en.data_ptr() if W else None, L.MEM_DEVICE))
-            return rows, en
-        audio = np.asarray(audio)
-        dt = np.float32 if audio.dtype == np.float32 else np.float64
-        audio = np.ascontiguousarray(audio, dt)
-        if audio.ndim != 2:
-            raise ValueError("audio must be [S, L]")
+        audio, audio_ptr, stride, f64 = M.rows(audio, _is_torch(audio), "audio must be [S, L]", audio=True)
         S, n = audio.shape
-        rows = np.empty((S, RT60_COLS), np.float64)
-        en = np.empty((S, n // W), np.float64) if W else None
+        rows = M.alloc(audio, (S, RT60_COLS), np.float64)
+        en = M.alloc(audio, (S, n // W), np.float64) if W else None
         if S:
-            self._eng._check(lib.omega_room_decay(self._eng._ctx, audio.ctypes.data, int(dt == np.float64), n, n, W, S,
-                                                 rows.ctypes.data, en.ctypes.data if W else None, L.MEM_HOST))
+            M.call(self._eng, L.lib().omega_room_decay, audio, audio_ptr, f64, stride, n, W, S, _ptr(rows), _ptr(en))
         return rows, en
 
     # -- RT60: the device rows finished on the host --

@@ -14,7 +14,9 @@ from typing import Any, Dict, List
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from . import _marshal as M
+from ._marshal import _is_torch, _ptr
+from .engine import utility_engine
 
 logger = logging.getLogger(__name__)
 COLUMNS = ("transients_detected", "attack_time", "punch_factor", "envelope_peak", "envelope_rms", "envelope_mean")
@@ -24,8 +26,7 @@ class TransientAnalyzer:
     def __init__(self, sample_rate: int = 48000, device: int = 0):
         self.sample_rate = sample_rate
         self.envelope_history = deque(maxlen=int(0.5 * 60))
-        self._eng = Engine([Resolution((20, 20000), 512, 256, 1.0)], sample_rate, min(20000, sample_rate / 2),
-                           target_bins=2, frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
 
     def analyze_batch(self, frames) -> np.ndarray:
         """frames [F, n] (float32 / float64; host numpy or device torch) -> [F, 6] float64 in COLUMNS order."""
@@ -37,18 +38,11 @@ class TransientAnalyzer:
             raise ValueError("frames must be [F, n]")
         F, n = frames.shape
         f64 = 1 if str(frames.dtype).endswith("float64") else 0
-        if dev:
-            import torch
-            out = torch.empty((F, len(COLUMNS)), dtype=torch.float64, device=frames.device)
-            self._eng._bind_stream(frames)
-            self._eng._check(L.lib().omega_transients(self._eng._ctx, frames.data_ptr(), f64, F, n, frames.stride(0),
-                                                      out.data_ptr(), L.MEM_DEVICE))
-            hist = out[:, 5].cpu().numpy()
-        else:
-            out = np.empty((F, len(COLUMNS)), np.float64)
-            self._eng._check(L.lib().omega_transients(self._eng._ctx, frames.ctypes.data, f64, F, n, n,
-                                                      out.ctypes.data, L.MEM_HOST))
-            hist = out[:, 5]
+        out = M.alloc(frames, (F, len(COLUMNS)), np.float64)
+        # (rows of this call may not overlap: a device batch is taken with the row stride it has)
+        M.call(self._eng, L.lib().omega_transients, frames, _ptr(frames), f64, F, n, frames.stride(0) if dev else n,
+               _ptr(out))
+        hist = out[:, 5].cpu().numpy() if dev else out[:, 5]
         self.envelope_history.extend(float(v) for v in hist)
         return out
 

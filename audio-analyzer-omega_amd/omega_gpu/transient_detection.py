@@ -39,7 +39,9 @@ from typing import Any, Callable, Dict, Optional, Tuple
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from . import _marshal as M
+from ._marshal import _is_torch, _ptr
+from .engine import utility_engine
 
 COLUMNS = ("flags", "envelope", "peak", "energy", "flux_sum", "flux", "novelty", "mag_sum", "hf_energy",
            "sign_diff", "peak_idx", "start_idx", "end_idx", "spec_sum", "spec_fsum", "rolloff_idx",
@@ -52,18 +54,15 @@ STATE_LEN = 4 + FLUX_BINS + 2 * PHASE_BINS
 def band_indices(sample_rate, n_bins: int) -> Tuple[int, ...]:
     """np.searchsorted(freqs, [0, 100, 250, 2000, fs / 2]) of :248-252 for a spectrum length, from the library."""
     r = (C.c_int32 * 5)()
-    code = L.lib().omega_tdetect_band_indices(float(sample_rate), int(n_bins), r)
-    if code != L.OK:
-        raise L.OmegaError(code, "omega_tdetect_band_indices: bad sample rate or bin count")
+    L.check_plain(L.lib().omega_tdetect_band_indices(float(sample_rate), int(n_bins), r),
+                  "omega_tdetect_band_indices: bad sample rate or bin count")
     return tuple(int(v) for v in r)
 
 
 class TransientDetectionPanel:
     def __init__(self, sample_rate, device: int = 0, clock: Callable[[], float] = time.time):
         self._host_init(sample_rate, clock)
-        fmax = min(20000, sample_rate / 2)
-        self._eng = Engine([Resolution((20, fmax), 512, 256, 1.0)], int(sample_rate), fmax, target_bins=2,
-                           frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
         assert L.lib().omega_tdetect_state_size() == STATE_LEN
 
     def _host_init(self, sample_rate, clock: Callable[[], float] = time.time) -> None:
@@ -133,55 +132,20 @@ class TransientDetectionPanel:
         wider spectra). state: what an earlier call returned for the stream, or None at its start. Returns
         ([F, len(COLUMNS)] float64, the new state): numpy for host input, device tensors for device input.
         Nothing of this object changes; F frames in one call equal F chained calls bit for bit."""
-        lib = L.lib()
-        if _is_torch(spectra):
-            import torch
-            if not _is_torch(frames):
-                raise ValueError("spectra and frames must both be device tensors or both host arrays")
-            if spectra.dtype != torch.float32:
-                spectra = spectra.float()
-            if spectra.dim() != 2 or frames.dim() != 2 or frames.shape[0] != spectra.shape[0]:
-                raise ValueError("spectra must be [F, K] and frames [F, m]")
-            if spectra.stride(1) != 1 or (spectra.shape[0] > 1 and spectra.stride(0) < 1):
-                spectra = spectra.contiguous()
-            if frames.dtype not in (torch.float32, torch.float64):
-                frames = frames.double()
-            if frames.stride(1) != 1 or (frames.shape[0] > 1 and frames.stride(0) < 1):
-                frames = frames.contiguous()
-            F, K = spectra.shape
-            m = frames.shape[1]
-            self._configure(K, m)
-            if state is not None:
-                state = torch.as_tensor(state, dtype=torch.float64, device=spectra.device).contiguous()
-                if state.numel() != STATE_LEN:
-                    raise ValueError(f"state must hold {STATE_LEN} values")
-            out = torch.empty((F, len(COLUMNS)), dtype=torch.float64, device=spectra.device)
-            new = torch.empty(STATE_LEN, dtype=torch.float64, device=spectra.device)
-            self._eng._bind_stream(spectra)
-            self._eng._check(lib.omega_tdetect_features(
-                self._eng._ctx, spectra.data_ptr(), spectra.stride(0) if F > 1 else K, frames.data_ptr(),
-                int(frames.dtype == torch.float64), F, frames.stride(0) if F > 1 else m,
-                state.data_ptr() if state is not None else None, new.data_ptr(), out.data_ptr(), L.MEM_DEVICE))
-            return out, new
-        spectra = np.ascontiguousarray(spectra, np.float32)
-        frames = np.asarray(frames)
-        frames = np.ascontiguousarray(frames if frames.dtype in (np.float32, np.float64) else frames.astype(np.float64))
-        if spectra.ndim != 2 or frames.ndim != 2 or frames.shape[0] != spectra.shape[0]:
-            raise ValueError("spectra must be [F, K] and frames [F, m]")
+        dev = _is_torch(spectra)
+        if dev and not _is_torch(frames):
+            raise ValueError(M.MIXED_SIDES)
+        spectra, spec_ptr, spec_stride, _ = M.rows(spectra, dev, M.SPECTRA_FRAMES)
+        frames, frame_ptr, frame_stride, f64 = M.rows(frames, dev, M.SPECTRA_FRAMES, audio=True)
+        if frames.shape[0] != spectra.shape[0]:
+            raise ValueError(M.SPECTRA_FRAMES)
         F, K = spectra.shape
-        m = frames.shape[1]
-        self._configure(K, m)
-        if state is not None:
-            if _is_torch(state):
-                state = state.detach().cpu().numpy()
-            state = np.ascontiguousarray(state, np.float64)
-            if state.size != STATE_LEN:
-                raise ValueError(f"state must hold {STATE_LEN} values")
-        out = np.empty((F, len(COLUMNS)), np.float64)
-        new = np.empty(STATE_LEN, np.float64)
-        self._eng._check(lib.omega_tdetect_features(
-            self._eng._ctx, spectra.ctypes.data, K, frames.ctypes.data, int(frames.dtype == np.float64), F, m,
-            state.ctypes.data if state is not None else None, new.ctypes.data, out.ctypes.data, L.MEM_HOST))
+        self._configure(K, frames.shape[1])
+        state = M.state_blob(state, spectra, STATE_LEN)
+        out = M.alloc(spectra, (F, len(COLUMNS)), np.float64)
+        new = M.alloc(spectra, (STATE_LEN,), np.float64)
+        M.call(self._eng, L.lib().omega_tdetect_features, spectra, spec_ptr, spec_stride, frame_ptr, f64, F,
+               frame_stride, _ptr(state), _ptr(new), _ptr(out))
         return out, new
 
     # -- the host part --

@@ -34,7 +34,9 @@ from typing import Any, Dict, Optional, Tuple
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from . import _marshal as M
+from ._marshal import _is_torch, _ptr
+from .engine import utility_engine
 
 COLUMNS = ("flags", "voice_start", "voice_end", "voice_energy", "total_energy", "formant_count",
            "f1_bin", "f2_bin", "f3_bin", "f4_bin", "f1_freq", "f2_freq", "f3_freq", "f4_freq",
@@ -45,18 +47,15 @@ FLAG_RANGE, FLAG_NO_ENERGY, FLAG_NONFINITE, FLAG_NO_PITCH = 1, 2, 4, 8
 def voice_bin_range(sample_rate, frame_len: int) -> Tuple[int, int]:
     """(voice_start, voice_end) of :64-67 for a frame length, from the library (no device)."""
     r = (C.c_int32 * 2)()
-    code = L.lib().omega_voice_bin_range(float(sample_rate), int(frame_len), r)
-    if code != L.OK:
-        raise L.OmegaError(code, "omega_voice_bin_range: bad sample rate or frame length")
+    L.check_plain(L.lib().omega_voice_bin_range(float(sample_rate), int(frame_len), r),
+                  "omega_voice_bin_range: bad sample rate or frame length")
     return int(r[0]), int(r[1])
 
 
 class VoiceDetectionPanel:
     def __init__(self, sample_rate, device: int = 0):
         self._host_init(sample_rate)
-        fmax = min(20000, sample_rate / 2)
-        self._eng = Engine([Resolution((20, fmax), 512, 256, 1.0)], int(sample_rate), fmax, target_bins=2,
-                           frame_size=512, device=device)
+        self._eng = utility_engine(sample_rate, device)
 
     def _host_init(self, sample_rate) -> None:
         """The state that needs no device (the tests drive the host logic on it alone): :14-51 minus drawing."""
@@ -105,45 +104,20 @@ class VoiceDetectionPanel:
         rows may overlap (an ``unfold`` view of a stream; a strided view of wider spectra). Returns
         [F, len(COLUMNS)] float64: numpy for host input, a device tensor for device input. The frames are
         independent and no state changes."""
-        lib = L.lib()
-        if _is_torch(spectra):
-            import torch
-            if not _is_torch(frames):
-                raise ValueError("spectra and frames must both be device tensors or both host arrays")
-            if spectra.dtype != torch.float32:
-                spectra = spectra.float()
-            if spectra.dim() != 2 or frames.dim() != 2 or frames.shape[0] != spectra.shape[0]:
-                raise ValueError("spectra must be [F, K] and frames [F, m]")
-            if spectra.stride(1) != 1 or (spectra.shape[0] > 1 and spectra.stride(0) < 1):
-                spectra = spectra.contiguous()
-            if frames.dtype not in (torch.float32, torch.float64):
-                frames = frames.double()
-            if frames.stride(1) != 1 or (frames.shape[0] > 1 and frames.stride(0) < 1):
-                frames = frames.contiguous()
-            F, K = spectra.shape
-            m = frames.shape[1]
-            self._configure(K, m)
-            out = torch.empty((F, len(COLUMNS)), dtype=torch.float64, device=spectra.device)
-            if F:
-                self._eng._bind_stream(spectra)
-                self._eng._check(lib.omega_voice_features(
-                    self._eng._ctx, spectra.data_ptr(), spectra.stride(0) if F > 1 else K, frames.data_ptr(),
-                    int(frames.dtype == torch.float64), m, frames.stride(0) if F > 1 else m, F, out.data_ptr(),
-                    L.MEM_DEVICE))
-            return out
-        spectra = np.ascontiguousarray(spectra, np.float32)
-        frames = np.asarray(frames)
-        frames = np.ascontiguousarray(frames if frames.dtype in (np.float32, np.float64) else frames.astype(np.float64))
-        if spectra.ndim != 2 or frames.ndim != 2 or frames.shape[0] != spectra.shape[0]:
-            raise ValueError("spectra must be [F, K] and frames [F, m]")
+        dev = _is_torch(spectra)
+        if dev and not _is_torch(frames):
+            raise ValueError(M.MIXED_SIDES)
+        spectra, spec_ptr, spec_stride, _ = M.rows(spectra, dev, M.SPECTRA_FRAMES)
+        frames, frame_ptr, frame_stride, f64 = M.rows(frames, dev, M.SPECTRA_FRAMES, audio=True)
+        if frames.shape[0] != spectra.shape[0]:
+            raise ValueError(M.SPECTRA_FRAMES)
         F, K = spectra.shape
         m = frames.shape[1]
         self._configure(K, m)
-        out = np.empty((F, len(COLUMNS)), np.float64)
+        out = M.alloc(spectra, (F, len(COLUMNS)), np.float64)
         if F:
-            self._eng._check(lib.omega_voice_features(self._eng._ctx, spectra.ctypes.data, K, frames.ctypes.data,
-                                                      int(frames.dtype == np.float64), m, m, F, out.ctypes.data,
-                                                      L.MEM_HOST))
+            M.call(self._eng, L.lib().omega_voice_features, spectra, spec_ptr, spec_stride, frame_ptr, f64, m,
+                   frame_stride, F, _ptr(out))
         return out
 
     def _row(self, audio_data, spectrum) -> np.ndarray:

@@ -10,13 +10,14 @@ independent channels and returns [n, C, 3] (level, display, peak). Drawing stays
 """
 from __future__ import annotations
 
-import ctypes as C
 import logging
 
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, Resolution, _is_torch
+from . import _marshal as M
+from ._marshal import _is_torch, _ptr
+from .engine import utility_engine
 
 logger = logging.getLogger(__name__)
 
@@ -29,8 +30,7 @@ class VUMeters:
         self.vu_reference_level = 0.125
         self.vu_peak_hold_time = 2.0
         self.n_channels = n_channels
-        self._eng = Engine([Resolution((20, 20000), 512, 256, 1.0)], sample_rate, min(20000, sample_rate / 2),
-                           target_bins=2, frame_size=512, n_channels=n_channels, device=device)
+        self._eng = utility_engine(sample_rate, device, n_channels=n_channels)
         self._last = np.tile([-60.0, -60.0, -60.0], (n_channels, 1))
         self._publish()
 
@@ -55,16 +55,14 @@ class VUMeters:
         dts = np.array(np.broadcast_to(np.asarray(dts, np.float64), (n,)))
         if dev:
             import torch
-            dt_dev = torch.as_tensor(dts, device=frames.device)
-            out = torch.empty((n, c, 3), dtype=torch.float64, device=frames.device)
-            self._eng._bind_stream(frames)
-            self._eng._check(L.lib().omega_vu_update(self._eng._ctx, frames.data_ptr(), f64, n, m, frames.stride(0),
-                                                     frames.stride(1), dt_dev.data_ptr(), out.data_ptr(), L.MEM_DEVICE))
-            return out
-        out = np.empty((n, c, 3), np.float64)
-        self._eng._check(L.lib().omega_vu_update(self._eng._ctx, frames.ctypes.data, f64, n, m, c * m, m,
-                                                 dts.ctypes.data, out.ctypes.data, L.MEM_HOST))
-        if n:
+            update_stride, channel_stride = frames.stride(0), frames.stride(1)
+            dts = torch.as_tensor(dts, device=frames.device)
+        else:
+            update_stride, channel_stride = c * m, m
+        out = M.alloc(frames, (n, c, 3), np.float64)
+        M.call(self._eng, L.lib().omega_vu_update, frames, _ptr(frames), f64, n, m, update_stride, channel_stride,
+               _ptr(dts), _ptr(out))
+        if n and not dev:  # (a device batch is not read back: the attributes follow host updates)
             self._last = out[-1].copy()
             self._publish()
         return out

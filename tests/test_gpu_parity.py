@@ -871,6 +871,30 @@ def test_meter_load_history_longer_than_windows():
     assert torch.equal(got, ref)
 
 
+def test_meter_load_history_refused_rows_leave_the_stream():
+    """load_meter_history validates dtype and shape before it binds the stream: a refused history, given
+    under another torch stream, leaves the context on the stream it had; an accepted one moves it."""
+    import ctypes
+    import torch
+    from omega_gpu import _lib as L
+    from omega_gpu import Engine, Resolution
+    e = Engine([Resolution((20, 20000), 512, 256, 1.0)], FS, 20000, 2, frame_size=512, n_channels=2)
+    stream_of = lambda: L.lib().omega_get_stream(e._ctx)  # noqa: E731
+    rows = torch.full((8, 2), -20.0, device="cuda")
+    e.load_meter_history(rows, rows)
+    before = stream_of()
+    side = torch.cuda.Stream()
+    assert ctypes.c_void_p(side.cuda_stream).value != before
+    with torch.cuda.stream(side):
+        for bad in (rows[:, 0], rows.double(), torch.full((8, 3), -20.0, device="cuda")):
+            with pytest.raises(ValueError, match="load_meter_history"):
+                e.load_meter_history(bad, bad)
+            assert stream_of() == before
+        e.load_meter_history(rows, rows)
+        assert stream_of() == ctypes.c_void_p(side.cuda_stream).value
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("n_l,n_t", [(0, 0), (1, 1), (40, 40), (100, 30), (3599, 59), (2500, 0)])
 def test_meter_load_history_equals_replay(n_l, n_t):
     """omega_meter_load_history writes the meter state of a stream with the given LUFS_inst / true-peak

@@ -307,6 +307,28 @@ def test_harmonic_truncation_null_audio_and_pointers():
 
 
 @pytest.mark.gpu
+def test_harmonic_broadcast_device_batch_is_copied():
+    """A device batch built by ``expand`` of one row (row stride 0) takes the common row rule: it is copied
+    and analysed, bit-equal to its ``.contiguous()`` copy. F = 3, K = 512 bins, m = 512 samples. (Before the
+    facades shared their marshalling this facade tested stride(1) alone and the library refused the batch
+    as a bad layout.)"""
+    import torch
+    fs, freqs, frames = group("app")
+    spec, audio = frames[0]
+    assert spec.shape == (512,)
+    spectra = torch.from_numpy(spec).cuda()[None, :].expand(3, 512)
+    batch = torch.from_numpy(audio[:512]).cuda()[None, :].expand(3, 512)
+    assert spectra.stride(0) == 0 and batch.stride(0) == 0
+    got = analyzer("app").analyze_frames(spectra, freqs, batch)
+    want = analyzer("app").analyze_frames(spectra.contiguous(), freqs, batch.contiguous())
+    for a, b in zip(got, want):
+        assert a.is_cuda and a.shape[0] == 3
+        np.testing.assert_array_equal(a.cpu().numpy(), b.cpu().numpy())
+    rows = got[0].cpu().numpy()
+    assert (rows[:, 0] > 0).all()  # (a series is found in every row: none is the zero row)
+
+
+@pytest.mark.gpu
 def test_harmonic_unsupported_and_invalid_shapes():
     """Shapes outside the supported table return OMEGA_EUNSUP with the message (no CPU fallback), bad
     tables OMEGA_EINVAL; a non-finite spectrum is flagged and gives the zero row."""

@@ -299,3 +299,38 @@ def test_pitch_device_memory_and_stream_view():
     np.testing.assert_array_equal(b, host)
     np.testing.assert_array_equal(an.detect_batch(view).cpu().numpy(), b)
     assert len(an.pitch_history) == 60
+
+
+@pytest.mark.gpu
+def test_pitch_broadcast_device_batch_is_copied():
+    """A device batch built by ``expand`` of one frame (row stride 0) takes the common row rule: it is
+    copied and analysed, bit-equal to its ``.contiguous()`` copy. F = 3 frames of n = 2048 samples. (Before
+    the facades shared their marshalling this facade tested stride(1) alone and the library refused the
+    batch as a bad layout.)"""
+    import torch
+    x = G()["t2048/x"][0]
+    assert x.shape == (2048,) and analyzer("t2048").yin_window_size <= 2048
+    batch = torch.from_numpy(x).cuda()[None, :].expand(3, 2048)
+    assert batch.stride(0) == 0
+    got = analyzer("t2048").detect_batch(batch)
+    want = analyzer("t2048").detect_batch(batch.contiguous())
+    assert got.is_cuda and tuple(got.shape) == (3, 10)
+    np.testing.assert_array_equal(got.cpu().numpy(), want.cpu().numpy())
+    rows = got.cpu().numpy()
+    assert (rows[:, 9] == 0).all() and (rows[:, 0] > 0).all()  # (every row is an estimate, not the zero row)
+    np.testing.assert_array_equal(rows[1:], rows[:1].repeat(2, axis=0))
+
+
+@pytest.mark.gpu
+def test_pitch_integer_device_samples_become_float64():
+    """Device samples that are neither float32 nor float64 are converted to float64, as the host path always
+    did (the device path used to hand their bytes to the library as float32): an int16 batch is bit-equal
+    to its float64 copy."""
+    import torch
+    x = G()["t2048/x"][:1]
+    pcm = torch.from_numpy(np.round(x * 32767 / np.abs(x).max()).astype(np.int16)).cuda()
+    got = analyzer("t2048").detect_batch(pcm)
+    want = analyzer("t2048").detect_batch(pcm.double())
+    np.testing.assert_array_equal(got.cpu().numpy(), want.cpu().numpy())
+    np.testing.assert_array_equal(got.cpu().numpy(), analyzer("t2048").detect_batch(pcm.cpu().numpy()))
+    assert got[0, 9] == 0 and 210 < float(got[0, 0]) < 230  # (the 220 Hz tone, not reinterpreted bytes)
