@@ -8,7 +8,8 @@
 // then whatever primes remain, factored on the host), one 256-thread workgroup per frame, ping-ponging
 // two complex buffers in LDS (global scratch above kAnyLdsMax points). Stage s with Ns = R_1..R_{s-1}:
 // output q of butterfly j = sum_r a[j + r N/R] T[r (k + q Ns) N/(Ns R) mod N], k = j mod Ns, written to
-// (j / Ns) Ns R + k + q Ns, T[m] = e^{-2 pi i m / N} (host table, float64 -> float32). Every output
+// (j / Ns) Ns R + k + q Ns, T[m] = e^{-2 pi i m / N} (host table, float64 -> float32; the stages of
+// a remaining prime sum in float64 with the unrounded table). Every output
 // sums its R inputs directly (N R complex multiply-adds per stage): O(N sum R) per transform, O(N^2)
 // for a prime N -- this path serves the lengths the fast kernels do not, not the batch hot path.
 //
@@ -23,7 +24,6 @@
 namespace omega {
 
 constexpr int kAnyThreads = 256;
-constexpr int kAnyF32Radix = 7;  // radices above it (the remaining primes) accumulate in float64
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -43,9 +43,13 @@ __device__ float2* any_fft(float2* a, float2* b, const AnyFftParams& p) {
       if (R > kAnyF32Radix) {
         // a large prime factor: R terms summed one after the other lose up to R eps / 2 in float32 (coherent
         // terms, e.g. the peak of a pulse: 5.9e-6 relative at R = 1021) -- float64 sums, rounded once
+        // with the factors of the float64 table: the rounding errors of the float32 one add up over the R
+        // terms to one offset common to all outputs (a prime N: every bin k != 0 of a constant frame gets
+        // sum_m (T32[m] - T[m]), 2e-6 of the DC bin at N = 6827, which the true peak's phases add up again)
         double ax = 0.0, ay = 0.0;
         for (int r = 0; r < R; ++r) {
-          const float2 v = a[j + r * NR], w = p.tw[e];
+          const float2 v = a[j + r * NR];
+          const double2 w = p.tw64[e];
           ax += (double)v.x * w.x - (double)v.y * w.y;
           ay += (double)v.x * w.y + (double)v.y * w.x;
           e += eq;

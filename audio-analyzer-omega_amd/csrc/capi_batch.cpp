@@ -777,6 +777,13 @@ int get_any_plan(omega_ctx* c, int N, omega_ctx::AnyPlan** out) {
       rot[m] = make_float2((float)std::cos(2 * kPi * (double)m / (4.0 * N)), (float)std::sin(2 * kPi * (double)m / (4.0 * N)));
     int e = upload(c, &pl.tw, tw);
     if (!e) e = upload(c, &pl.rot, rot);
+    if (!e && !pl.radix.empty() && pl.radix.back() > kAnyF32Radix) {
+      // a stage of R terms summed in float64 keeps its precision only with unrounded factors: the rounding
+      // errors of the float32 table add up over the R terms to the same offset in every output
+      std::vector<double2> tw64(N);
+      for (int m = 0; m < N; ++m) tw64[m] = make_double2(std::cos(2 * kPi * m / N), -std::sin(2 * kPi * m / N));
+      e = upload(c, &pl.tw64, tw64);
+    }
     if (e) return e;
     it = c->any_plans.emplace(N, std::move(pl)).first;
   }
@@ -792,6 +799,7 @@ int run_any(omega_ctx* c, AnyFftParams p, int truepeak) {
   p.n_stages = (int)pl->radix.size();
   for (int s = 0; s < p.n_stages; ++s) p.radix[s] = pl->radix[s];
   p.tw = pl->tw;
+  p.tw64 = pl->tw64;
   p.rot = pl->rot;
   for (int ph = 0; ph < 4; ++ph) p.nyq_cos[ph] = (float)std::cos(kPi * ph / 4.0);
   const int64_t n = p.n;

@@ -376,6 +376,7 @@ struct omega_ctx {
   struct AnyPlan {
     std::vector<int> radix;
     float2* tw = nullptr;
+    double2* tw64 = nullptr;
     float2* rot = nullptr;
   };
   std::map<int, AnyPlan> any_plans;

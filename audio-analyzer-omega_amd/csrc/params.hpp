@@ -728,6 +728,7 @@ struct BassZoomParams {
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch
+constexpr int kAnyF32Radix = 7;   // radices above it (the remaining primes) accumulate in float64
 struct AnyFftParams {
   const float* x;           // frame f at x + f * frame_stride
   int64_t frame_stride;
@@ -736,6 +737,7 @@ struct AnyFftParams {
   int n_stages;
   int radix[kAnyMaxStages];
   const float2* tw;         // [N] e^{-2 pi i m / N}
+  const double2* tw64;      // [N] the same table unrounded, for the radices above kAnyF32Radix (nullptr: none)
   const float2* rot;        // [3 (N / 2) + 1] e^{2 pi i m / (4N)} (true peak)
   float nyq_cos[4];         // cos(pi p / 4)
   int phases;               // true peak: bit p set for each phase p in 1..3

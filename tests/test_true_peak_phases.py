@@ -17,8 +17,9 @@ only as far as FACTOR x dev <= eps32 log2(4N) relative (cap_db), with the measur
 recorded here. The sentinel frames return exactly -100.0 or a finite value on the reference's side.
 
 Paths by frame length (omega_true_peak_os / tp_launch / run_any): 512-4096 launch_truepeak (Stockham),
-8192 and 16384 launch_truepeak_rf (register FFT), 1-7, 16, 100, 1000, 1021, 4800 anyfft.hip in LDS
-(radix-4, radix-2/5, a prime single stage), 10000 anyfft.hip on global scratch; the batch kernel's
+8192 and 16384 launch_truepeak_rf (register FFT), 1-7, 16, 100, 1000, 1021, 4800, 6826 anyfft.hip in LDS
+(radix-4, radix-2/5, a prime single stage; 6826 = 2 x 3413 fills the 160 KiB), 6827 (prime) and 10000
+anyfft.hip on global scratch; the batch kernel's
 true-peak role and the captured-graph layout at 16384 through process_frames; omega_calculate_lufs at
 2048 and 4800.
 
@@ -30,7 +31,10 @@ the float32 nearest the expectation at -199.17 dB (half an ulp there is 7.6e-6);
 deviations are 2e-7 to 2.3e-6. Before this module the prime length 1021 summed its single 1021-term
 stage in float32 and was 6.5e-5 dB (5.9e-6 relative, 4.6 x cap) off on the above-silence pulse, and
 20.0f * log10f(peak) was up to an ulp of the dB value off for an exact peak (DC: 8.1e-7 dB against half an
-ulp of 4.8e-7); anyfft.hip now sums radices above 7 in float64 and the three kernels share tp_db().
+ulp of 4.8e-7); anyfft.hip now sums radices above 7 in float64 and the three kernels share tp_db(). At 6827 those sums
+still took the float32 twiddle table and `dc` was 2.40e-5 dB (4x) / 1.73e-5 dB (2x, bar 1.70e-5) off, the
+table's rounding errors adding up to one offset in every bin; with the float64 table 1.4e-7 dB, and
+6826 / 6827 3.3e-6 / 3.6e-6 dB at worst (the above-silence frames again).
 """
 import ctypes as C
 
@@ -42,7 +46,8 @@ from oracle import omega_ref as R
 
 FS = 48000
 EPS32 = float(np.finfo(np.float32).eps)
-LENGTHS = [1, 2, 3, 5, 7, 16, 100, 512, 1000, 1021, 1024, 2048, 4096, 4800, 8192, 10000, 16384]
+LENGTHS = [1, 2, 3, 5, 7, 16, 100, 512, 1000, 1021, 1024, 2048, 4096, 4800, 6826, 6827, 8192, 10000,
+           16384]
 FACTORS = (4, 2, 1)
 
 
