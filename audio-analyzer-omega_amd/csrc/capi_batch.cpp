@@ -1,23 +1,19 @@
 // libomega.so host side: the batch launch path -- omega_process_frames down to launch_batch, with the
 // meter segments, the counters and the stream layout -- and the meter, true-peak and weighting entry
-// points that share its state. The per-step path is whole in this translation unit.
+// points that share its state. The per-step path is whole in this translation unit, but for the grid
+// arithmetic: batch_plan.hpp's plan_batch lays out the grid of a call's shape as a pure function, and this
+// file enqueues it. enqueue_frames decides the call's shape once (batch layout, meters in the grid,
+// pipelined, overlapped) and hands the batch to one of three enqueue functions, each with its own
+// launch-failure handling: enqueue_batch_chunks (no meters, or a batch longer than kChunkFrames: meter
+// query kernels), enqueue_batch_direct (this call's meter segment as the grid's last) and
+// enqueue_batch_pipelined (the previous call's segment in the grid, this call's left pending).
 
+#include "batch_plan.hpp"
 #include "host.hpp"
 
 namespace {
 
 constexpr int kChunkFrames = kMeterChunk;
-constexpr int kBatchWaves = 8;  // waves of a batch_kernel workgroup (rfkern.hip kBatchThreads / 64)
-// meter workgroups of the batch grid at most: they wait (spinning) for the meter prep kernel, which
-// may be dispatched after them and needs a CU with at most one batch workgroup resident (1024 threads
-// and 72.6 KiB of LDS beside one 512-thread, 71.9 KiB batch workgroup). 64 waiting workgroups hold at
-// most 64 of the 512 batch slots, so at least 192 CUs keep a slot that other roles free as they
-// finish. (Round 1: one meter workgroup per 8 outputs of a 4096-frame batch took every slot and waited
-// until the poll bound expired.)
-#ifndef OMEGA_METER_WGS
-#define OMEGA_METER_WGS 64  // (measured: 16 and 32 slower, profiles/r04_ab_meter_wgs.txt)
-#endif
-constexpr int kMeterWgs = OMEGA_METER_WGS;
 
 int get_kw_tab(omega_ctx* c, int M, int L, BiquadTab** out) {
   const auto key = std::make_pair(M, L);
@@ -40,8 +36,7 @@ int get_kw_tab(omega_ctx* c, int M, BiquadTab** out) { return get_kw_tab(c, M, k
 
 // True-peak kernel choice: the register-FFT kernel for 8192- and 16384-sample frames, the LDS-pass
 // kernel for the other powers of two.
-hipError_t tp_launch(omega_ctx* c, int W, const SpectralParams& sp, hipStream_t s) {
-  (void)c;
+hipError_t tp_launch(int W, const SpectralParams& sp, hipStream_t s) {
   if (W == 16384 || W == 8192) return launch_truepeak_rf(W, sp, s);
   return launch_truepeak(W, sp, s);
 }
@@ -170,13 +165,10 @@ int flush_meters(omega_ctx* c, hipStream_t on) {
     if (int e = join_batches(c)) return e;
   if (!c->pend) return 0;
   HIPC(c, hipSetDevice(c->device));
-  BatchPlan bp{};
-  bp.q_begin = 0;
-  bp.q_n = c->pend_nq;
-  bp.seg_start[0] = bp.seg_start[1] = bp.multi_start = c->pend_nq;  // (no other workgroups)
   SpectralParams sp{};
   KWeightParams kp{};
-  const hipError_t le = launch_batch(sp, kp, bp, c->pend_mq, c->pend_nq, on ? on : c->stream);
+  const hipError_t le =
+      launch_batch(sp, kp, plan_segment_only(c->pend_nq), c->pend_mq, c->pend_nq, on ? on : c->stream);
   if (le != hipSuccess) return fail(c, OMEGA_EHIP, "meter segment launch: %s", hipGetErrorString(le));
   c->pend = false;
   c->seg_par[c->pend_par] = c->seg_issued + (unsigned)c->pend_nq;
@@ -226,7 +218,7 @@ bool batch_eligible(omega_ctx* c, const SpectralParams& sp, const KWeightParams&
   return true;
 }
 
-// The default layout for 16384-sample frames. On `s`: one batch_kernel launch (BatchPlan: K-weighting
+// The default layout for 16384-sample frames. On `s`: one batch_kernel launch (plan_batch: K-weighting
 // and 16384-point-resolution workgroups mixed, then the true peaks, then the small resolutions, then --
 // for a batch of at most kChunkFrames frames per channel -- the meter aggregates as the grid's last
 // segment; pipelined, the previous call's, between the true peaks and the small resolutions). On
@@ -244,177 +236,39 @@ bool batch_eligible(omega_ctx* c, const SpectralParams& sp, const KWeightParams&
 // true-peak meter as a batch role (86-88), the true-peak meter by the batch's last true-peak workgroup,
 // joined there (86.2 vs 81.1, round 3). The in-grid meter segment measured even with the query kernels
 // (step 79.4-80.6 vs 79.0-79.4 us) at two fewer launches per call (host enqueue 13-17 vs 22-27 us).
-int enqueue_batch(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int64_t n_frames, const float* lufs,
-                  const float* tp, double* meters, hipStream_t s, int mr, bool do_tp, bool do_kw, bool fold) {
-  (void)W;
-  const int64_t n = sp.n_cf;
+
+// What plan_batch reads of the call; the meter segment (q_n, q_before_multi) is the enqueue function's.
+BatchShape batch_shape(const SpectralParams& sp, int mr, bool do_tp, bool do_kw) {
+  BatchShape sh{};
+  sh.n_cf = sp.n_cf;
+  sh.n_res = sp.n_res;
+  for (int r = 0; r < sp.n_res; ++r) sh.res[r] = {sp.res[r].n, sp.comb_out || sp.res[r].mag_out};
+  sh.mr = mr;
+  sh.do_kw = do_kw;
+  sh.do_tp = do_tp;
+  return sh;
+}
+
+int plan_or_fail(omega_ctx* c, const BatchShape& sh, BatchPlan* bp, int* grid) {
+  if (plan_batch(sh, bp, grid))
+    return fail(c, OMEGA_EINVAL, "batch of %lld channel-frames too large", (long long)sh.n_cf);
+  return 0;
+}
+
+// The batch without a meter segment: no meters, or a batch longer than kChunkFrames, whose chunks chain
+// through the per-context scratch and keep the query kernels. Before the batch, per chunk on fork[0]: the
+// prep (the first waits for the K-weighting count) and the LUFS query, counting itself in; the batch on
+// `s`; behind it on `s` the true-peak queries, the last joining the LUFS queries' count.
+int enqueue_batch_chunks(omega_ctx* c, const SpectralParams& sp, KWeightParams kp, const BatchShape& sh,
+                         int64_t n_frames, const float* lufs, const float* tp, double* meters, hipStream_t s) {
   BatchPlan bp{};
-  int seg[2][3], ns[2] = {0, 0};
-  auto add = [&](int sg, int role, bool on) {
-    if (on) seg[sg][ns[sg]++] = role;
-  };
-  // (measured: the true peaks in segment 0 beside the K-weighting, the 16384-point resolution in
-  // segment 1, with or without the small resolutions before it: step 73.5-75.1 vs 68.8-70.5 us)
-  // (measured, round 5, pipelined step on one box: the K-weighting beside the true peaks with the
-  // 16384-point resolution after them, or the true peaks beside the 16384-point resolution with the
-  // K-weighting after them, 65.3-67.3 us against 65.3-67.1 for this order: the same)
-  add(0, 0, do_kw);        // segment 0: K-weighting and the 16384-point resolution, groups of 8 frames
-  add(0, 2, mr >= 0);
-  add(1, 1, do_tp);        // segment 1: the true peaks
-  const int64_t groups = (n + 7) / 8;
-  int64_t end = 0;
-  for (int sg = 0; sg < 2; ++sg) {
-    bp.n_roles[sg] = ns[sg] ? ns[sg] : 1;
-    for (int i = 0; i < 3; ++i) bp.roles[sg][i] = i < ns[sg] ? seg[sg][i] : 0;
-    end += ns[sg] ? 8 * ns[sg] * groups : 0;
-    if (end > 0x7FFFFFFF) return fail(c, OMEGA_EINVAL, "batch of %lld channel-frames too large", (long long)n);
-    bp.seg_begin[sg + 1] = (int)end;
-  }
-  bp.mr_res = mr < 0 ? 0 : mr;
-  int64_t nwg = 0;
-  for (int r = 0; r < sp.n_res; ++r) {
-    if (r == mr || (!sp.comb_out && !sp.res[r].mag_out)) continue;
-    const int K = sp.res[r].n / 2;
-    const int G = K / 16 < 64 ? 64 : K / 16;  // threads_for<K>() for K <= 4096
-    const int fpw = 512 / G;
-    bp.multi.res[bp.multi.n_seg] = r;
-    bp.multi.wg_begin[bp.multi.n_seg] = (int)nwg;
-    ++bp.multi.n_seg;
-    nwg += (n + fpw - 1) / fpw;
-  }
-  // the meter aggregates of a one-chunk batch as the grid's last segment (batch_meter_role): the prep
-  // kernel on fork[0] (it waits for the K-weighting count) counts itself in, the true-peak workgroups
-  // count themselves in, the meter workgroups wait for both; longer batches chain their chunks through
-  // the per-context scratch and keep the query kernels
-  const bool in_grid = meters && do_tp && do_kw && n_frames > 0 && n_frames <= kChunkFrames;
-  const int64_t n_mq = in_grid ? std::min<int64_t>((n + kBatchWaves - 1) / kBatchWaves, kMeterWgs) : 0;
-  // meter pipelining (fold): this launch runs the PREVIOUS call's meter segment as its last workgroups
-  // (its inputs are complete: that batch ended before this one starts; the prep that reads this batch's
-  // values still runs beside it on the side stream) and leaves its own pending
-  fold = fold && in_grid;
-  const int64_t q_n = fold ? (c->pend ? c->pend_nq : 0) : n_mq;
-  // grid order: segment 0 | segment 1 | small resolutions (measured: the small resolutions between the
-  // segments, step 80.4-81.3 vs 76.6-77.5 us, round 4); segment 0 in the period-8 role order
-  // (BatchPlan::pat: batch kernel 65.7-66.1 vs 70.9-71.5 us)
-  bp.pat = 1;
-  bp.multi_n = (int)nwg;
-  bp.seg_start[0] = 0;
-  bp.seg_start[1] = bp.seg_begin[1];
-  bp.multi_start = bp.seg_begin[2];
-  const int64_t body_end = end + nwg;
-  // the grid's last segment unpipelined (measured: placed before the small resolutions it holds 64
-  // slots from ~50 us on while it waits and the step is no shorter, 77.4-79.2 vs 77.0-78.0 us);
-  // pipelined, it waits for nothing (first in the grid it delayed the true peaks: step 68-69 vs 64-65
-  // us without meters)
-  bp.q_begin = (int)body_end;
-  bp.q_n = (int)q_n;
-  // pipelined (the previous call's segment: it waits for nothing), the segment goes after the true peaks
-  // and before the small resolutions instead: longest-first in the tail, its ~9-10 us workgroups ahead
-  // of the 7-12 us resolution ones (pipelined step 63.5-64.4 vs 64.9-65.2 us last, four alternations on
-  // one box, tools/ab.sh, outputs bitwise equal direct and pipelined; on a second box 62.8-64.7 vs
-  // 64.6-65.1 last and 62.8-64.4 after the 8192-point resolution).
-  // Unpipelined it stays last: before the small resolutions its waiting workgroups cost the in-call
-  // step 70.4-73.1 vs 66.9-67.6 us
-  if (fold) bp.q_begin = bp.multi_start;
-  // (measured, round 5: the pipelined segment between segment 0 and the true peaks instead, step
-  // 65.3-67.1 vs 66.5-66.6 us on one box: no difference)
-  const int64_t grid = body_end + q_n;
-  if (grid > 0x7FFFFFFF) return fail(c, OMEGA_EINVAL, "batch of %lld channel-frames too large", (long long)n);
-  MeterPrepParams mq{};
+  int grid = 0;
+  if (int e = plan_or_fail(c, sh, &bp, &grid)) return e;
   std::vector<MeterPrepParams> mc;
-  if (in_grid) {
-    const int a = c->cur;
-    const unsigned seg_par_was = c->seg_par[a ^ 1];
-    // the pending segment (parity a ^ 1) is enqueued by this launch: the prep's target for the state it
-    // reads (meter_chunks) counts it
-    if (fold && c->pend) c->seg_par[c->pend_par] = c->seg_issued + (unsigned)c->pend_nq;
-    const int cur_was = c->cur;  // (meter_chunks flips the state parity)
-    mc = meter_chunks(c, lufs, tp, n_frames, meters);
-    // the prep on the side stream, waiting for this batch's K-weighting count
-    MeterPrepParams p = mc[0];
-    p.q_done = c->d_kw_done + 3;
-    // pipelined: the prep polls generation-tagged words the K-weighting workgroups store without a
-    // drain or a count; unpipelined: the count
-    const size_t mir_n = (size_t)kChunkFrames * c->cfg.n_channels;
-    if (fold && !c->d_mirror) {
-      HIPC(c, hipMalloc(&c->d_mirror, 2 * mir_n * sizeof(unsigned long long)));
-      HIPC(c, hipMemset(c->d_mirror, 0, 2 * mir_n * sizeof(unsigned long long)));
-    }
-    const bool mirror = fold;
-    const unsigned gen_was = c->mirror_gen;
-    if (mirror) {
-      // consecutive launches alternate parity: a prep still reading one parity while the next launch's
-      // K-weighting writes the other (it waits for nothing), and done before the launch after that
-      // (whose predecessor's segment waits for it)
-      c->mirror_gen = c->mirror_gen == 0xFFFFFFFFu ? 2u : c->mirror_gen + 1;
-      kp.lufs_mirror = c->d_mirror + (c->mirror_gen & 1) * mir_n;
-      kp.mirror_gen = c->mirror_gen;
-      p.lufs_mirror = kp.lufs_mirror;
-      p.mirror_gen = c->mirror_gen;
-    } else {
-      kp.kw_done = c->d_kw_done;
-      c->kw_issued += (unsigned)n;
-      p.wait_ctr = c->d_kw_done;
-      p.wait_target = c->kw_issued;
-    }
-    if (fold)
-      if (int e = tail_init(c)) return e;
-    const bool tail = fold && c->tail_ok > 0;
-    if (tail) bp.tail_ctr = c->d_tail;
-    // unpipelined: the prep before the batch (it must be resident while the batch runs: its segment
-    // waits for it); pipelined: after it, behind the stream wait -- enqueued before the batch, a wait
-    // whose stream shared a hardware queue with the batch's would block the batch behind it for ever
-    if (!fold) HIPC(c, launch_meter_prep(p, c->fork[0]));
-    c->side_meters = true;
-    mq = mc[0];
-    mq.start_ctr = c->d_kw_done + 3;
-    mq.start_target = c->prep_issued + (unsigned)p.C;
-    // the meter segment's wait for the true peaks (each true-peak workgroup stores its value
-    // write-through and counts in); a pipelined segment runs in a later launch, after this batch ended
-    if (!fold) {
-      sp.tp_done = c->d_kw_done + 2;
-      mq.join_ctr = c->d_kw_done + 2;
-      mq.join_target = c->tp_issued + (unsigned)n;
-    }
-    const hipError_t le = launch_batch(sp, kp, bp, fold ? c->pend_mq : mq, (int)grid, s);
-    if (le != hipSuccess) {
-      // the prep kernel already waits for this batch's count: publish it (see below)
-      if (!fold) {
-        (void)hipMemcpy(c->d_kw_done, &c->kw_issued, sizeof(unsigned), hipMemcpyHostToDevice);
-        c->prep_issued += (unsigned)p.C;
-      } else {
-        // (no prep waits for this launch: nothing was enqueued; the generation goes back so the next
-        // launch takes the other parity)
-        c->mirror_gen = gen_was;
-        c->seg_par[a ^ 1] = seg_par_was;  // (the pending segment stays pending)
-        c->cur = cur_was;                 // (no prep writes the other parity's state)
-      }
-      return fail(c, OMEGA_EHIP, "batch launch: %s", hipGetErrorString(le));
-    }
-    if (!fold) c->tp_issued += (unsigned)n;
-    if (tail) {
-      HIPC(c, hipStreamWaitValue32(c->fork[0], c->d_tail, c->tail_issued + 1, hipStreamWaitValueGte, 0xFFFFFFFFu));
-      ++c->tail_issued;
-    }
-    if (fold) HIPC(c, launch_meter_prep(p, c->fork[0]));
-    c->side_meters = true;
-    c->prep_issued += (unsigned)p.C;
-    if (fold) {
-      if (c->pend) c->seg_issued += (unsigned)c->pend_nq;
-      c->pend = true;
-      c->pend_mq = mq;
-      c->pend_nq = (int)n_mq;
-      c->pend_par = a;
-    } else {
-      c->seg_par[a] = c->seg_issued + (unsigned)n_mq;
-      c->seg_issued += (unsigned)n_mq;
-    }
-    return 0;
-  }
   if (meters) {
     mc = meter_chunks(c, lufs, tp, n_frames, meters);
     kp.kw_done = c->d_kw_done;
-    c->kw_issued += (unsigned)n;
+    c->kw_issued += (unsigned)sp.n_cf;
     for (size_t i = 0; i < mc.size(); ++i) {
       MeterPrepParams p = mc[i];
       if (i == 0) {
@@ -431,7 +285,7 @@ int enqueue_batch(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int6
     }
   }
   if (grid > 0) {
-    const hipError_t le = launch_batch(sp, kp, bp, mq, (int)grid, s);
+    const hipError_t le = launch_batch(sp, kp, bp, MeterPrepParams{}, grid, s);
     if (le != hipSuccess) {
       // the prep kernel already waits for this batch's count: publish it, so that it (and every later
       // call's target) stays in step with the device counter instead of timing out
@@ -451,8 +305,124 @@ int enqueue_batch(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int6
   return 0;
 }
 
-// The per-batch work: layout 3 (enqueue_batch) where eligible, otherwise the full-chip kernels back to
-// back on `s` (K-weighting first); the meter aggregates' prep and LUFS query kernels (one or two
+// The meter aggregates of a one-chunk batch as the grid's last segment (batch_meter_role), this call's own:
+// the prep kernel on fork[0] (it waits for the K-weighting count) counts itself in, the true-peak
+// workgroups count themselves in, the meter workgroups wait for both. The prep goes before the batch: it
+// must be resident while the batch runs (its segment waits for it).
+int enqueue_batch_direct(omega_ctx* c, SpectralParams sp, KWeightParams kp, BatchShape sh, int64_t n_frames,
+                         const float* lufs, const float* tp, double* meters, hipStream_t s) {
+  const int64_t n = sp.n_cf;
+  const int n_mq = meter_segment_wgs(n);
+  sh.q_n = n_mq;
+  sh.q_before_multi = false;
+  BatchPlan bp{};
+  int grid = 0;
+  if (int e = plan_or_fail(c, sh, &bp, &grid)) return e;
+  const int a = c->cur;  // (meter_chunks flips the state parity)
+  const MeterPrepParams m0 = meter_chunks(c, lufs, tp, n_frames, meters)[0];
+  // the prep on the side stream, waiting for this batch's K-weighting count
+  MeterPrepParams p = m0;
+  p.q_done = c->d_kw_done + 3;
+  kp.kw_done = c->d_kw_done;
+  c->kw_issued += (unsigned)n;
+  p.wait_ctr = c->d_kw_done;
+  p.wait_target = c->kw_issued;
+  HIPC(c, launch_meter_prep(p, c->fork[0]));
+  c->side_meters = true;
+  MeterPrepParams mq = m0;
+  mq.start_ctr = c->d_kw_done + 3;
+  mq.start_target = c->prep_issued + (unsigned)p.C;
+  // the meter segment's wait for the true peaks (each true-peak workgroup stores its value write-through
+  // and counts in)
+  sp.tp_done = c->d_kw_done + 2;
+  mq.join_ctr = c->d_kw_done + 2;
+  mq.join_target = c->tp_issued + (unsigned)n;
+  const hipError_t le = launch_batch(sp, kp, bp, mq, grid, s);
+  if (le != hipSuccess) {
+    // the prep kernel already waits for this batch's count: publish it, so that it (and every later
+    // call's target) stays in step with the device counter instead of timing out
+    (void)hipMemcpy(c->d_kw_done, &c->kw_issued, sizeof(unsigned), hipMemcpyHostToDevice);
+    c->prep_issued += (unsigned)p.C;
+    return fail(c, OMEGA_EHIP, "batch launch: %s", hipGetErrorString(le));
+  }
+  c->tp_issued += (unsigned)n;
+  c->prep_issued += (unsigned)p.C;
+  c->seg_par[a] = c->seg_issued + (unsigned)n_mq;
+  c->seg_issued += (unsigned)n_mq;
+  return 0;
+}
+
+// Meter pipelining: this launch runs the PREVIOUS call's meter segment in its grid (its inputs are
+// complete: that batch ended before this one starts, so it waits for nothing) and leaves its own
+// pending. The prep that reads this batch's values runs beside it on the side stream: it polls
+// generation-tagged words the K-weighting workgroups store without a drain or a count,
+// and goes AFTER the batch, behind the stream wait for the grid's last workgroup -- enqueued before the
+// batch, a wait whose stream shared a hardware queue with the batch's would block the batch behind it
+// for ever. `s`: the caller's stream, or an overlapped call's batch stream (nothing is pending there:
+// enqueue_frames launches each call's segment behind its batch).
+int enqueue_batch_pipelined(omega_ctx* c, const SpectralParams& sp, KWeightParams kp, BatchShape sh,
+                            int64_t n_frames, const float* lufs, const float* tp, double* meters, hipStream_t s) {
+  sh.q_n = c->pend ? c->pend_nq : 0;
+  sh.q_before_multi = true;
+  BatchPlan bp{};
+  int grid = 0;
+  if (int e = plan_or_fail(c, sh, &bp, &grid)) return e;
+  const int a = c->cur;  // (meter_chunks flips the state parity)
+  const unsigned seg_par_was = c->seg_par[a ^ 1];
+  // the pending segment (parity a ^ 1) is enqueued by this launch: the prep's target for the state it
+  // reads (meter_chunks) counts it
+  if (c->pend) c->seg_par[c->pend_par] = c->seg_issued + (unsigned)c->pend_nq;
+  const MeterPrepParams m0 = meter_chunks(c, lufs, tp, n_frames, meters)[0];
+  MeterPrepParams p = m0;
+  p.q_done = c->d_kw_done + 3;
+  const size_t mir_n = (size_t)kChunkFrames * c->cfg.n_channels;
+  if (!c->d_mirror) {
+    HIPC(c, hipMalloc(&c->d_mirror, 2 * mir_n * sizeof(unsigned long long)));
+    HIPC(c, hipMemset(c->d_mirror, 0, 2 * mir_n * sizeof(unsigned long long)));
+  }
+  // consecutive launches alternate parity: a prep still reading one parity while the next launch's
+  // K-weighting writes the other (it waits for nothing), and done before the launch after that
+  // (whose predecessor's segment waits for it)
+  const unsigned gen_was = c->mirror_gen;
+  c->mirror_gen = c->mirror_gen == 0xFFFFFFFFu ? 2u : c->mirror_gen + 1;
+  kp.lufs_mirror = c->d_mirror + (c->mirror_gen & 1) * mir_n;
+  kp.mirror_gen = c->mirror_gen;
+  p.lufs_mirror = kp.lufs_mirror;
+  p.mirror_gen = c->mirror_gen;
+  if (int e = tail_init(c)) return e;
+  const bool tail = c->tail_ok > 0;
+  if (tail) bp.tail_ctr = c->d_tail;
+  c->side_meters = true;
+  // this call's segment, for the launch that runs it: it starts once the prep has counted in (its batch
+  // has ended by then: no wait for the true peaks)
+  MeterPrepParams mq = m0;
+  mq.start_ctr = c->d_kw_done + 3;
+  mq.start_target = c->prep_issued + (unsigned)p.C;
+  const hipError_t le = launch_batch(sp, kp, bp, c->pend_mq, grid, s);
+  if (le != hipSuccess) {
+    // (no prep waits for this launch: nothing was enqueued; the generation goes back so the next
+    // launch takes the other parity)
+    c->mirror_gen = gen_was;
+    c->seg_par[a ^ 1] = seg_par_was;  // (the pending segment stays pending)
+    c->cur = a;                       // (no prep writes the other parity's state)
+    return fail(c, OMEGA_EHIP, "batch launch: %s", hipGetErrorString(le));
+  }
+  if (tail) {
+    HIPC(c, hipStreamWaitValue32(c->fork[0], c->d_tail, c->tail_issued + 1, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    ++c->tail_issued;
+  }
+  HIPC(c, launch_meter_prep(p, c->fork[0]));
+  c->prep_issued += (unsigned)p.C;
+  if (c->pend) c->seg_issued += (unsigned)c->pend_nq;
+  c->pend = true;
+  c->pend_mq = mq;
+  c->pend_nq = meter_segment_wgs(sp.n_cf);
+  c->pend_par = a;
+  return 0;
+}
+
+// The per-batch work: layout 3 (the enqueue_batch_* functions) where eligible, otherwise the full-chip
+// kernels back to back on `s` (K-weighting first); the meter aggregates' prep and LUFS query kernels (one or two
 // workgroups per channel: latency-bound) run on fork[0] beside the resolution and true-peak kernels,
 // the true-peak meter after the true peaks on `s`. (Concurrent full-chip kernels lose to this: 512
 // channel-frames are exactly two rounds of 256 CUs, and a CU held by another kernel pushes a third.)
@@ -465,9 +435,12 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
                       sp.res[3].mag_out;
   int mr = -1;
   const bool batch = c->layout == 3 && batch_eligible(c, sp, kp, W, do_res, s, &mr);
+  // the meter aggregates in the batch's grid: a one-chunk batch with both of their inputs
+  const bool in_grid = batch && meters && do_tp && do_kw && n_frames > 0 && n_frames <= kChunkFrames;
   // a pending meter segment goes first: folded into this batch's launch when it has an in-grid meter
   // segment of its own, else on its own
-  const bool fold = pipe && batch && meters && do_tp && do_kw && n_frames > 0 && n_frames <= kChunkFrames;
+  const bool fold = pipe && in_grid;
+  const BatchShape sh = batch ? batch_shape(sp, mr, do_tp, do_kw) : BatchShape{};
   // overlapped (omega_ctx::bs): the batch and, behind it, its own meter segment on a batch stream
   if (fold && c->bs[0])
     if (int e = tail_init(c)) return e;
@@ -498,7 +471,7 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
     if (c->tail_issued)
       HIPC(c, hipStreamWaitValue32(b, c->d_tail, c->tail_issued, hipStreamWaitValueGte, 0xFFFFFFFFu));
     const int err = [&]() -> int {
-      if (int e = enqueue_batch(c, sp, kp, W, n_frames, lufs, tp, meters, b, mr, do_tp, do_kw, true)) return e;
+      if (int e = enqueue_batch_pipelined(c, sp, kp, sh, n_frames, lufs, tp, meters, b)) return e;
       // this call's meter segment, a launch of its own behind its batch: it polls the prep's count (the
       // prep is enqueued: fork[0], behind the tail wait) and runs beside the next call's batch. Segments
       // run in call order (each reads the true-peak history the one before rolled)
@@ -526,7 +499,9 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
     ++c->bs_idx;
     return 0;
   }
-  if (batch) return enqueue_batch(c, sp, kp, W, n_frames, lufs, tp, meters, s, mr, do_tp, do_kw, fold);
+  if (fold) return enqueue_batch_pipelined(c, sp, kp, sh, n_frames, lufs, tp, meters, s);
+  if (in_grid) return enqueue_batch_direct(c, sp, kp, sh, n_frames, lufs, tp, meters, s);
+  if (batch) return enqueue_batch_chunks(c, sp, kp, sh, n_frames, lufs, tp, meters, s);
   if (do_kw) HIPC(c, launch_kweight(W, kp, s));
   std::vector<MeterPrepParams> mc;
   if (meters) {
@@ -543,7 +518,7 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
     HIPC(c, hipEventRecord(c->ev_join[0], c->fork[0]));
   }
   if (do_res) HIPC(c, c->res_independent ? launch_mrfft_independent(sp, s) : launch_mrfft(sp, s));
-  if (do_tp) HIPC(c, tp_launch(c, W, sp, s));
+  if (do_tp) HIPC(c, tp_launch(W, sp, s));
   for (MeterPrepParams p : mc) {
     p.parts = 2;
     HIPC(c, launch_meter_query(p, s));
@@ -863,7 +838,7 @@ int omega_true_peak_os(omega_ctx* c, const float* x, int64_t n, int32_t m, int32
   sp.rot = rot;
   sp.tp_phases = oversampling == 4 ? 0xE : (oversampling == 2 ? 0x4 : 0);
   sp.tp_done = c->tp_count_to;  // (omega_calculate_lufs)
-  HIPC(c, tp_launch(c, m, sp, c->stream));
+  HIPC(c, tp_launch(m, sp, c->stream));
   return h.finish();
 } catch (...) {
   return guard_fail(c);
