@@ -1,17 +1,141 @@
-// The grid of one batch_kernel launch (BatchPlan, params.hpp) as a pure function of the call's shape:
-// integer arithmetic only -- no context, no device, no HIP call -- so a plan can be evaluated, and a change
-// to it stated, on the CPU (tests/test_batch_plan.py against tools/model/batch_plan_model.py). Host only:
-// capi_batch.cpp enqueues what plan_batch lays out. The measured-and-rejected orders are recorded beside
-// the decisions they belong to.
+// The grid of one batch_kernel launch, both directions, as pure functions: plan_batch lays the workgroups
+// of a call's shape out (BatchPlan), decode_block maps a blockIdx back to the work it does. Integer
+// arithmetic only -- no context, no device memory, no HIP call -- so a plan and its decode can be evaluated,
+// and a change to them stated, on the CPU (tests/test_batch_plan.py against tools/model/batch_plan_model.py).
+// plan_batch and its helpers are host code: capi_batch.cpp enqueues what they lay out. decode_block and the
+// pieces it is made of compile for host and device: rfkern.hip's batch_body runs the pieces, the CPU test
+// runs decode_block. The measured-and-rejected orders are recorded beside the decisions they
+// belong to.
 #pragma once
-
-#include <algorithm>
 
 #include "params.hpp"
 
 namespace omega {
 
-constexpr int kBatchWaves = 8;  // waves of a batch_kernel workgroup (rfkern.hip kBatchThreads / 64)
+constexpr int kBatchThreads = 512;               // one batch_kernel workgroup
+constexpr int kBatchWaves = kBatchThreads / 64;
+
+// The thread group that transforms one frame of an at most 8192-point resolution (threads_for<K>() of
+// fft.hpp for K = fft_size / 2 <= 4096; rfkern.hip batch_multi holds the two to each other): a workgroup
+// of T threads runs T / small_res_group(fft_size) frames of it.
+constexpr int small_res_group(int fft_size) { return fft_size / 32 < 64 ? 64 : fft_size / 32; }
+
+// Segments of one mrfft_multi_kernel launch: resolution res[s] owns workgroups
+// [wg_begin[s], wg_begin[s+1]) (the last one up to the grid end).
+struct MultiPlan {
+  int n_seg;
+  int res[4];
+  int wg_begin[4];
+};
+
+// One launch for the per-channel-frame work of a batch of 16384-sample frames (rfkern.hip
+// batch_kernel), 512-thread workgroups. Roles: 0 K-weighting + LUFS_inst, 1 true peak, 2 the
+// 16384-point resolution (mr_res). Two segments of role groups, the small resolutions (multi) and the
+// meter segment [q_begin, q_begin + q_n); decode_block below is the map from a blockIdx to its work.
+//   [seg_begin[s], seg_begin[s + 1])  the length of segment s: groups of 8 workgroups, one role and 8
+//       consecutive channel-frames each, so the roles of a frame land on one XCD (blockIdx % 8). (The
+//       hardware places an XCD's workgroups in blockIdx order round-robin over its 4 shader engines and
+//       holds the next one until its engine has room, so with two roles each engine runs one role and
+//       the engines of the short 16384-point-resolution workgroups idle ~5 us behind the K-weighting
+//       ones: 80 % of the slot-time used, tools/wgtrace.py. Role chunks of one workgroup per CU fill
+//       90 % of it, but the shader clock drops from ~2120 to ~1890 MHz and the launch takes longer: the
+//       batch runs at the chip's power limit, so idle slots are not free time. DESIGN.md §8.)
+//   pat: the group order of a two-role segment: 0 alternating groups (each shader engine runs one
+//       role), 1 the period-8 order A B A B B A B A (seen by one XCD through blockIdx % 8, its engines
+//       get the roles in turn, so an engine's short workgroups do not wait behind another's long
+//       ones; the product's order, round 4: batch kernel 71.3 -> 65.9 us).
+//   seg_start / multi_start / multi_n: where segment s and the small resolutions begin in the grid.
+struct BatchPlan {
+  int seg_begin[3];
+  int n_roles[2];
+  int roles[2][3];
+  int mr_res;
+  MultiPlan multi;
+  int q_begin, q_n;
+  unsigned* tail_ctr;  // (meter pipelining) the last workgroup adds 1 at its start: see host.hpp omega_ctx::d_tail
+  int pat;
+  int seg_start[2];
+  int multi_start, multi_n;
+};
+
+// What one workgroup of the grid does.
+enum BatchWorkKind : int {
+  kBatchNothing,  // past every range
+  kBatchMeter,    // workgroup `index` of the q_n of the meter segment
+  kBatchRole,     // role `which` (0, 1, 2) of channel-frame `index`; in the last group of 8 it may be past n_cf
+  kBatchSmallRes  // workgroup `index` of resolution `which`
+};
+struct BatchWork {
+  int kind, which;
+  int64_t index;
+};
+
+// blockIdx b of a grid laid out by plan_batch or plan_segment_only -> its work (decode_block): three range
+// tests in this order, each answering "which of mine, or -1", and for the roles and the small resolutions
+// the work of a block that passed its test. Only operations that mean the same on host and device.
+// batch_body runs the same pieces in the same order, each test with its own early exit: called as one
+// function there, the compiler keeps the merged result and dispatches on it a second time, which costs the
+// kernel spilled SGPRs and a measurable part of its speed.
+
+// the meter segment: workgroup q of q_n, or -1
+__host__ __device__ __forceinline__ int meter_index(const BatchPlan& bp, int b) {
+  return b >= bp.q_begin && b < bp.q_begin + bp.q_n ? b - bp.q_begin : -1;
+}
+
+// the role segment b lies in, or -1
+__host__ __device__ __forceinline__ int role_segment(const BatchPlan& bp, int b) {
+  const int len0 = bp.seg_begin[1], len1 = bp.seg_begin[2] - bp.seg_begin[1];
+  return (b >= bp.seg_start[0] && b < bp.seg_start[0] + len0) ? 0
+         : (b >= bp.seg_start[1] && b < bp.seg_start[1] + len1) ? 1 : -1;
+}
+
+// block b of role segment sg: role 0, 1 or 2 of a channel-frame (past n_cf in the last group of 8, perhaps)
+__host__ __device__ __forceinline__ BatchWork role_work(const BatchPlan& bp, int sg, int b) {
+  // workgroup j of the segment: group j / 8 of 8 channel-frames, frame j % 8 of it
+  const int j = b - bp.seg_start[sg], nr = bp.n_roles[sg];
+  int role;
+  int64_t cf;
+  if (nr == 2 && bp.pat == 1) {
+    // period-8 group order A B A B B A B A (0x5A: the B positions); a group's index among its role's
+    // groups = 4 per period + the same-role positions before it
+    const int g = j >> 3, per = g & 7, rb = (0x5A >> per) & 1;
+    role = bp.roles[sg][rb];
+    const int idx = 4 * (g >> 3) + __builtin_popcount((rb ? 0x5A : 0xA5) & ((1 << per) - 1));
+    cf = (int64_t)idx * 8 + (j & 7);
+  } else {  // the roles in turn, group by group
+    role = bp.roles[sg][(j >> 3) % nr];
+    cf = (int64_t)(j / (8 * nr)) * 8 + (j & 7);
+  }
+  return {kBatchRole, role, cf};
+}
+
+// b's index among the small resolutions' workgroups, or -1
+__host__ __device__ __forceinline__ int small_res_index(const BatchPlan& bp, int b) {
+  // (the meter segment may sit before or inside the small resolutions: the workgroups after it shift by
+  // q_n)
+  const int w = b - bp.multi_start -
+                (b >= bp.q_begin + bp.q_n && bp.q_begin < bp.multi_start + bp.multi_n ? bp.q_n : 0);
+  return w < 0 || w >= bp.multi_n ? -1 : w;
+}
+
+// small-resolution workgroup w: which resolution's, and which of that resolution's
+__host__ __device__ __forceinline__ BatchWork small_res_work(const BatchPlan& bp, int w) {
+  const MultiPlan& mp = bp.multi;
+  int s = 0;
+  while (s + 1 < mp.n_seg && w >= mp.wg_begin[s + 1]) ++s;
+  return {kBatchSmallRes, mp.res[s], w - mp.wg_begin[s]};
+}
+
+__host__ __device__ __forceinline__ BatchWork decode_block(const BatchPlan& bp, int b) {
+  const int q = meter_index(bp, b);
+  if (q >= 0) return {kBatchMeter, 0, q};
+  const int sg = role_segment(bp, b);
+  if (sg >= 0) return role_work(bp, sg, b);
+  const int w = small_res_index(bp, b);
+  if (w < 0) return {kBatchNothing, 0, 0};
+  return small_res_work(bp, w);
+}
+
 // meter workgroups of the batch grid at most: they wait (spinning) for the meter prep kernel, which
 // may be dispatched after them and needs a CU with at most one batch workgroup resident (1024 threads
 // and 72.6 KiB of LDS beside one 512-thread, 71.9 KiB batch workgroup). 64 waiting workgroups hold at
@@ -44,7 +168,8 @@ constexpr int kPlanSegmentTooLarge = 1, kPlanGridTooLarge = 2;  // plan_batch: p
 
 // The workgroups of the meter segment over n_cf outputs: one wave per output, at most kMeterWgs.
 inline int meter_segment_wgs(int64_t n_cf) {
-  return (int)std::min<int64_t>((n_cf + kBatchWaves - 1) / kBatchWaves, kMeterWgs);
+  const int64_t wgs = (n_cf + kBatchWaves - 1) / kBatchWaves;
+  return wgs < kMeterWgs ? (int)wgs : kMeterWgs;
 }
 
 // A grid of nq meter workgroups and nothing else (a pending segment launched on its own).
@@ -86,9 +211,7 @@ inline int plan_batch(const BatchShape& sh, BatchPlan* out, int* grid_out) {
   int64_t nwg = 0;
   for (int r = 0; r < sh.n_res; ++r) {
     if (r == sh.mr || !sh.res[r].wanted) continue;
-    const int K = sh.res[r].n / 2;
-    const int G = K / 16 < 64 ? 64 : K / 16;  // threads_for<K>() for K <= 4096
-    const int fpw = 512 / G;
+    const int fpw = kBatchThreads / small_res_group(sh.res[r].n);
     bp.multi.res[bp.multi.n_seg] = r;
     bp.multi.wg_begin[bp.multi.n_seg] = (int)nwg;
     ++bp.multi.n_seg;

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/omega.h"
+#include "batch_plan.hpp"
 #include "design.hpp"
 #include "params.hpp"
 

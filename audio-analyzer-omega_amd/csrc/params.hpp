@@ -243,44 +243,6 @@ struct CombineParams {
   float* out;           // [n_cf, T]
 };
 
-// Segments of one mrfft_multi_kernel launch: resolution res[s] owns workgroups
-// [wg_begin[s], wg_begin[s+1]) (the last one up to the grid end).
-struct MultiPlan {
-  int n_seg;
-  int res[4];
-  int wg_begin[4];
-};
-
-// One launch for the per-channel-frame work of a batch of 16384-sample frames (rfkern.hip
-// batch_kernel), 512-thread workgroups. Roles: 0 K-weighting + LUFS_inst, 1 true peak, 2 the
-// 16384-point resolution (mr_res). Two segments of role groups, then the small resolutions:
-//   [seg_begin[s], seg_begin[s + 1])  groups of 8 * n_roles[s] workgroups; workgroup b of the segment
-//       runs role roles[s][(b / 8) % n_roles[s]] of channel-frame 8 (b / (8 n_roles[s])) + b % 8, so
-//       the roles of a frame land on one XCD (blockIdx % 8). (The hardware places an XCD's workgroups
-//       in blockIdx order round-robin over its 4 shader engines and holds the next one until its
-//       engine has room, so with two roles each engine runs one role and the engines of the short
-//       16384-point-resolution workgroups idle ~5 us behind the K-weighting ones: 80 % of the slot-time
-//       used, tools/wgtrace.py. Role chunks of one workgroup per CU fill 90 % of it, but the shader
-//       clock drops from ~2120 to ~1890 MHz and the launch takes longer: the batch runs at the chip's
-//       power limit, so idle slots are not free time. DESIGN.md §8.)
-//   pat: the group order of a two-role segment: 0 alternating groups (each shader engine runs one
-//       role), 1 the period-8 order A B A B B A B A (seen by one XCD through blockIdx % 8, its engines
-//       get the roles in turn, so an engine's short workgroups do not wait behind another's long
-//       ones; the product's order, round 4: batch kernel 71.3 -> 65.9 us).
-//   seg_start / multi_start / multi_n: where segment s and the small resolutions begin in the grid.
-struct BatchPlan {
-  int seg_begin[3];
-  int n_roles[2];
-  int roles[2][3];
-  int mr_res;
-  MultiPlan multi;
-  int q_begin, q_n;
-  unsigned* tail_ctr;  // (meter pipelining) the last workgroup adds 1 at its start: see host.hpp omega_ctx::d_tail
-  int pat;
-  int seg_start[2];
-  int multi_start, multi_n;
-};
-
 // Fused spectrum analysis (cfg3): windowed rfft magnitude (A13) -> log-band max (A10) and raw
 // chromagram (A12) of each frame, one pass over the frame.
 struct SpectraParams {

@@ -25,6 +25,7 @@ OMEGA_WGTRACE_DECL
 OMEGA_MARKS_DECL
 }  // namespace omega
 
+#include "batch_plan.hpp"
 #include "kw.hpp"
 #include "meter_query.hpp"
 #include "regfft.hpp"
@@ -734,20 +735,20 @@ hipError_t launch_truepeak_rf(int W, const SpectralParams& p, hipStream_t s, int
   return hipGetLastError();
 }
 
-// ---- one launch per batch of 16384-sample frames (BatchPlan, params.hpp) ----
+// ---- one launch per batch of 16384-sample frames (BatchPlan, batch_plan.hpp) ----
 // The K-weighting, true-peak, 16384-point-resolution and small-resolution workgroups of a batch share
 // one grid instead of running as back-to-back full-chip kernels: every role is 512 threads with at most
 // lds_bytes<8192>() of LDS (two workgroups per CU), so a CU mixes roles -- the latency-bound
 // K-weighting scans and resolution epilogues beside the VALU-bound true-peak transforms -- and there
 // are no kernel boundaries (ramp-up / tail) between the stages. K-weighting comes first so the meter
-// aggregates on the side stream can start while the transforms run.
-constexpr int kBatchThreads = 512;
+// aggregates on the side stream can start while the transforms run. (kBatchThreads: batch_plan.hpp.)
 
 // <= 8192-point resolution frames by groups of threads_for<K>() threads (mrfft_frame, spectral.hpp):
 // 2 frames of 8192 points, 4 of 4096, 8 of 2048 / 1024 / 512 per workgroup
 template <int K>
 __device__ __forceinline__ void batch_multi(const SpectralParams& p, int r, int64_t wg, int tid, float2* smem) {
   constexpr int G = threads_for<K>();
+  static_assert(G == small_res_group(2 * K), "plan_batch counts this resolution's workgroups by another group size");
   constexpr int FPW = kBatchThreads / G;
   static_assert(FPW * K * sizeof(float2) <= lds_bytes<8192>(), "LDS of one batch workgroup");
   const int grp = tid / G;
@@ -776,13 +777,14 @@ __device__ __forceinline__ void batch_kw_role(const KWeightParams& kp, int64_t c
 // 8 q + w + 8 nq, ... = (frame o / C, channel o % C). Unpipelined the segment is the grid's last: its
 // workgroups are dispatched after every other role of the batch, so their waits cannot hold back the
 // batch work they wait for (pipelined, the previous call's segment waits for nothing and is dispatched
-// after the true peaks, ahead of the small resolutions: capi_batch.cpp enqueue_batch): first
+// after the true peaks, ahead of the small resolutions: batch_plan.hpp plan_batch): first
 // (bounded) until the meter prep kernel on the side stream has counted in (it has waited for the
 // batch's K-weighting count), then the LUFS meters; then until every true-peak workgroup has counted
 // in, then the true-peak meter and the roll of the true-peak history. The batch completes only
 // after both, so the caller's stream needs no join kernel and no stream event. nq is at most
-// kMeterWgs (the host's cap): the waiting workgroups must leave room for the prep kernel, which may be
-// dispatched after them and needs a CU with at most one batch workgroup resident (capi_batch.cpp kMeterWgs).
+// kMeterWgs (batch_plan.hpp: the cap the three enqueue_batch_* paths of capi_batch.cpp plan with): the
+// waiting workgroups must leave room for the prep kernel, which may be dispatched after them and needs a
+// CU with at most one batch workgroup resident.
 __device__ __forceinline__ void batch_meter_role(const MeterPrepParams& mp, int q, int nq, int tid) {
   const int64_t n_out = mp.n_frames * mp.C, step = (int64_t)nq * (kBatchThreads / 64);
   const int64_t o0 = (int64_t)q * (kBatchThreads / 64) + (tid >> 6);
@@ -833,31 +835,19 @@ __device__ __forceinline__ void batch_body(const SpectralParams& sp, const KWeig
   // the meter prep (host.hpp omega_ctx::d_tail)
   if (bp.tail_ctr && b == (int)gridDim.x - 1 && tid == 0)
     __hip_atomic_fetch_add(bp.tail_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (b >= bp.q_begin && b < bp.q_begin + bp.q_n) {
-    batch_meter_role(mq, b - bp.q_begin, bp.q_n, tid);
+  // (batch_plan.hpp: the grid's layout and its inverse; decode_block's pieces in decode_block's order)
+  const int q = meter_index(bp, b);
+  if (q >= 0) {
+    batch_meter_role(mq, q, bp.q_n, tid);
     OMEGA_WG_END(4);
     return;
   }
-
-  const int len0 = bp.seg_begin[1], len1 = bp.seg_begin[2] - bp.seg_begin[1];
-  const int sg = (b >= bp.seg_start[0] && b < bp.seg_start[0] + len0) ? 0
-                 : (b >= bp.seg_start[1] && b < bp.seg_start[1] + len1) ? 1 : -1;
+  const int sg = role_segment(bp, b);
   if (sg >= 0) {
-    const int j = b - bp.seg_start[sg], nr = bp.n_roles[sg];
-    int role;
-    int64_t cf;
-    if (nr == 2 && bp.pat == 1) {
-      // period-8 group order A B A B B A B A (0x5A: the B positions); a group's index among its role's
-      // groups = 4 per period + the same-role positions before it
-      const int g = j >> 3, per = g & 7, rb = (0x5A >> per) & 1;
-      role = bp.roles[sg][rb];
-      const int idx = 4 * (g >> 3) + __popc((rb ? 0x5A : 0xA5) & ((1 << per) - 1));
-      cf = (int64_t)idx * 8 + (j & 7);
-    } else {
-      role = bp.roles[sg][(j >> 3) % nr];
-      cf = (int64_t)(j / (8 * nr)) * 8 + (j & 7);
-    }
-    if (cf >= sp.n_cf) return;
+    const BatchWork wk = role_work(bp, sg, b);
+    const int role = wk.which;
+    const int64_t cf = wk.index;
+    if (cf >= sp.n_cf) return;  // (the last group of 8)
     if (role == 0) {
       batch_kw_role(kp, cf, tid, smem);
     } else if (role == 1) {
@@ -868,16 +858,11 @@ __device__ __forceinline__ void batch_body(const SpectralParams& sp, const KWeig
     OMEGA_WG_END(role);
     return;
   }
-  const MultiPlan& mp = bp.multi;
-  // (the meter segment may sit before or inside the small resolutions: the workgroups after it shift by
-  // q_n)
-  const int w = b - bp.multi_start -
-                (b >= bp.q_begin + bp.q_n && bp.q_begin < bp.multi_start + bp.multi_n ? bp.q_n : 0);
-  if (w < 0 || w >= bp.multi_n) return;
-  int s = 0;
-  while (s + 1 < mp.n_seg && w >= mp.wg_begin[s + 1]) ++s;
-  const int r = mp.res[s];
-  const int64_t wg = w - mp.wg_begin[s];
+  const int w = small_res_index(bp, b);
+  if (w < 0) return;
+  const BatchWork wk = small_res_work(bp, w);
+  const int r = wk.which;
+  const int64_t wg = wk.index;
   float2* buf = reinterpret_cast<float2*>(smem);
   switch (sp.res[r].n) {
     case 512: batch_multi<256>(sp, r, wg, tid, buf); break;

@@ -21,6 +21,7 @@ namespace omega {
 OMEGA_STAMPS_DECL
 }  // namespace omega
 
+#include "batch_plan.hpp"
 #include "spectral.hpp"
 
 namespace omega {
@@ -254,9 +255,7 @@ hipError_t launch_mrfft_independent(const SpectralParams& p, hipStream_t s) {
       if (e != hipSuccess) return e;
       continue;
     }
-    const int K = n / 2;
-    const int G = K / 16 < 64 ? 64 : K / 16;  // threads_for<K>() for K <= 4096
-    const int fpw = kMultiThreads / G;
+    const int fpw = kMultiThreads / small_res_group(n);
     mp.res[mp.n_seg] = r;
     mp.wg_begin[mp.n_seg] = nwg;
     ++mp.n_seg;

@@ -1,9 +1,12 @@
-// The batch grid plan on the CPU (tests/test_batch_plan.py): reads one shape per line from standard input,
+// The batch grid on the CPU (tests/test_batch_plan.py): reads one shape per line from standard input,
 // evaluates csrc/batch_plan.hpp on it and prints every BatchPlan field and the grid, one case per line.
 //   P n_cf do_kw do_tp mr q_n q_before_multi n_res {fft_size wanted} x n_res   -> plan_batch
 //   S nq                                                                       -> plan_segment_only
 //   M n_cf                                                                     -> meter_segment_wgs
-// No device and no context: the header is host arithmetic only.
+// A D before a P or S case prints, instead of the fields, what decode_block (the pieces batch_body runs,
+// composed) makes of every block of the planned grid: numbers only, "code grid" and then "kind which index" per block 0..grid-1 (none
+// for a refused plan), all on the case's line.
+// No device and no context: the header is integer arithmetic only.
 #include <cinttypes>
 #include <cstdio>
 
@@ -29,9 +32,23 @@ static void dump(int code, const BatchPlan& bp, int grid) {
   std::printf(" multi_start=%d multi_n=%d\n", bp.multi_start, bp.multi_n);
 }
 
+static void dump_decode(int code, const BatchPlan& bp, int grid) {
+  std::printf("%d %d", code, grid);
+  for (int b = 0; code == 0 && b < grid; ++b) {
+    const BatchWork wk = decode_block(bp, b);
+    std::printf(" %d %d %" PRId64, wk.kind, wk.which, wk.index);
+  }
+  std::printf("\n");
+}
+
 int main() {
   char kind;
+  bool decode = false;
   while (std::scanf(" %c", &kind) == 1) {
+    if (kind == 'D') {
+      decode = true;
+      continue;
+    }
     if (kind == 'M') {
       int64_t n = 0;
       if (std::scanf("%" SCNd64, &n) != 1) return 2;
@@ -39,7 +56,7 @@ int main() {
     } else if (kind == 'S') {
       int nq = 0;
       if (std::scanf("%d", &nq) != 1) return 2;
-      dump(0, plan_segment_only(nq), nq);
+      (decode ? dump_decode : dump)(0, plan_segment_only(nq), nq);
     } else if (kind == 'P') {
       BatchShape sh{};
       int kw = 0, tp = 0, first = 0;
@@ -57,10 +74,11 @@ int main() {
       BatchPlan bp{};
       int grid = -1;
       const int code = plan_batch(sh, &bp, &grid);
-      dump(code, bp, grid);
+      (decode ? dump_decode : dump)(code, bp, grid);
     } else {
       return 2;
     }
+    decode = false;
   }
   return 0;
 }

@@ -1,9 +1,11 @@
-"""The batch grid plan (csrc/batch_plan.hpp: plan_batch, plan_segment_only, meter_segment_wgs) on the CPU:
-tests/abi/batch_plan_dump.cpp, a stand-alone host program, evaluates the header on a table of shapes, and
-every BatchPlan field and the grid must equal tools/model/batch_plan_model.py's. For every plan the
+"""The batch grid (csrc/batch_plan.hpp: plan_batch, plan_segment_only, meter_segment_wgs, decode_block) on
+the CPU: tests/abi/batch_plan_dump.cpp, a stand-alone host program, evaluates the header on a table of
+shapes, and every BatchPlan field and the grid must equal tools/model/batch_plan_model.py's. For every plan the
 invariants the kernel relies on are checked as well: the segments, the small resolutions' ranges and the
 meter segment partition [0, grid); each small resolution owns ceil(n / frames per workgroup) workgroups;
-every role of a channel-frame sits at a blockIdx congruent to the frame's index modulo 8, once."""
+every role of a channel-frame sits at a blockIdx congruent to the frame's index modulo 8, once. The same
+program runs decode_block, the composition of the pieces the kernel decodes a block with, over every block
+of every planned grid, and what it returns must be the model's work for that block."""
 import itertools
 import os
 import shutil
@@ -86,6 +88,22 @@ def dump(tmp_path_factory):
             out.append({k: [int(x) for x in v.split(",")] if "," in v else int(v) for k, v in kv.items()})
         assert len(out) == len(lines)
         return out
+
+    def decode(lines):
+        """decode_block of every block of each line's plan: [(code, grid, [grid, 3] kind / which / index)]"""
+        r = subprocess.run([exe], input="".join("D " + ln + "\n" for ln in lines), capture_output=True, text=True,
+                           timeout=60)
+        assert r.returncode == 0, r.stdout[-500:] + r.stderr[-500:]
+        v = np.fromstring(r.stdout, dtype=np.int64, sep=" ")
+        out, at = [], 0
+        for _ in lines:
+            code, grid = int(v[at]), int(v[at + 1])
+            n = 3 * grid if code == 0 else 0
+            out.append((code, grid, v[at + 2:at + 2 + n].reshape(-1, 3)))
+            at += 2 + n
+        assert at == len(v)
+        return out
+    run.decode = decode
     return run
 
 
@@ -145,6 +163,52 @@ def test_segment_only_plan(dump):
         f, grid = M.segment_only(nq)
         _assert_equal(got, f, grid, nq)
         assert M.ranges(f, grid) == [(0, nq, ("meter",))]
+
+
+NOTHING, METER, ROLE, SMALL_RES = range(4)  # BatchWorkKind
+
+
+def _model_decode(f, grid):
+    """[grid, 3] kind / which / index of every block from the model's ranges and segment_work, and how many
+    of the ranges claim each block"""
+    want = np.full((grid, 3), -1, dtype=np.int64)
+    claims = np.zeros(grid, dtype=np.int64)
+    for a, b, what in M.ranges(f, grid):
+        claims[a:b] += 1
+        if what[0] == "meter":    # q counts 0..q_n-1 in order
+            want[a:b] = np.stack([np.full(b - a, METER), np.zeros(b - a, np.int64), np.arange(b - a)], axis=1)
+        elif what[0] == "seg":
+            role, cf = M.segment_work(f, what[1])
+            want[a:b] = np.stack([np.full(b - a, ROLE), role, cf], axis=1)
+        else:                     # a resolution's workgroups count 0..count-1 in grid order
+            want[a:b] = np.stack([np.full(b - a, SMALL_RES), np.full(b - a, what[1]), np.arange(b - a)], axis=1)
+    return want, claims
+
+
+def _assert_decode(got, f, grid, what):
+    code, got_grid, work = got
+    assert (code, got_grid) == (0, grid), what
+    want, claims = _model_decode(f, grid)
+    assert np.all(claims == 1), (what, np.flatnonzero(claims != 1)[:8])
+    assert not np.any(work[:, 0] == NOTHING), (what, np.flatnonzero(work[:, 0] == NOTHING)[:8])
+    bad = np.flatnonzero(np.any(work != want, axis=1))
+    assert bad.size == 0, (what, bad[:8], work[bad[:8]], want[bad[:8]])
+    assert len(np.unique(work, axis=0)) == grid, what  # no work claimed by two blocks
+
+
+def test_decode_block_inverts_the_plan(dump):
+    """The kernel's blockIdx -> work map (decode_block: batch_body runs the pieces it is composed of, in its
+    order), block by block over every planned grid: the meter blocks count q = 0..q_n-1, the role blocks have the model's role and
+    channel-frame, each small resolution's blocks count its workgroups in grid order -- with the meter
+    segment before them, after them and absent -- and no block decodes to nothing or to another's work."""
+    cases = _cases()
+    assert len(cases) == 1512 and {(q > 0, first) for *_, q, first in cases} == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    for case, got in zip(cases, dump.decode([_line(c) for c in cases])):
+        n, kw, tp, mr, res, q, first = case
+        _, f, grid = M.plan(n, res, mr, bool(kw), bool(tp), q, bool(first))
+        _assert_decode(got, f, grid, case)
+    for nq, got in zip((1, 64), dump.decode(["S 1", "S 64"])):
+        _assert_decode(got, *M.segment_only(nq), nq)
 
 
 def test_meter_segment_workgroups(dump):

@@ -1270,16 +1270,19 @@ def test_graph_replay_matches_direct_launch():
                 assert torch.equal(a[k], b[k]), k
 
 
-def test_batch_layout_ragged_and_partial_outputs():
+@pytest.mark.parametrize("n_frames", [13, 33])
+def test_batch_layout_ragged_and_partial_outputs(n_frames):
     """The default layout (one batch_kernel launch: K-weighting, true-peak / 16384-point pairs, the small
     resolutions; meter prep waiting on the K-weighting count) against the side-meter layout (separate
     kernels, stream events): a channel-frame count that is not a multiple of the 8-frame pair groups,
     per-resolution magnitudes and the weighted signal, subsets of the stages, and meter state carried
-    over consecutive calls -- bitwise equal."""
+    over consecutive calls -- bitwise equal. 13 stereo frames are 8 role groups of segment 0, one period
+    of its A B A B B A B A order; 33 are 18 groups, two periods and part of a third (decode_block's
+    4 (g >> 3) term), with a last group of 2."""
     import torch
     from omega_gpu import Engine, NORTHSTAR_RESOLUTIONS
     from omega_gpu import _lib as L
-    x = torch.from_numpy(S.cfg2_batch(13)).cuda()
+    x = torch.from_numpy(S.cfg2_batch(n_frames)).cuda()
     calls = [dict(meters=True, mags=True, weighted=True), dict(meters=True), dict(true_peak=False),
              dict(combined=False), dict(lufs=False), dict(meters=True, mags=[0])]
     res = []
@@ -1288,7 +1291,7 @@ def test_batch_layout_ragged_and_partial_outputs():
         eng._check(L.lib().omega_set_graphs(eng._ctx, flags))
         seq = []
         for kw in calls:
-            o = eng.process_frames(x, 13, 2 * 16384, 16384, **kw)
+            o = eng.process_frames(x, n_frames, 2 * 16384, 16384, **kw)
             torch.cuda.synchronize()
             seq.append({k: v.clone() for k, v in o.items()})
         res.append(seq)

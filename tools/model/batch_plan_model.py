@@ -1,7 +1,8 @@
-"""Index model of the batch grid (csrc/params.hpp BatchPlan, csrc/batch_plan.hpp plan_batch): where every
+"""Index model of the batch grid (csrc/batch_plan.hpp BatchPlan, plan_batch, decode_block): where every
 workgroup of one batch_kernel launch sits, from the call's shape alone, and -- the other way round -- which
-work a blockIdx decodes to as the BatchPlan comment states it. Plain integers (Python's: no overflow), so
-tests/test_batch_plan.py can hold the header to it field by field and check what the kernel relies on:
+work a blockIdx decodes to. Plain integers (Python's: no overflow), so tests/test_batch_plan.py can hold
+the header to it, the plan field by field and the kernel's decode block by block, and check what the kernel
+relies on:
 the ranges partition the grid, every small resolution has its workgroups, and the roles of a channel-frame
 share blockIdx % 8 (one XCD).
 
@@ -73,7 +74,7 @@ def segment_only(nq):
     return f, nq
 
 
-# ---- blockIdx -> work, as the BatchPlan comment has it ----
+# ---- blockIdx -> work (decode_block is held to these) ----
 
 PERIOD8 = [0, 1, 0, 1, 1, 0, 1, 0]  # pat 1: the group order A B A B B A B A of a two-role segment
 
