@@ -1,12 +1,13 @@
 // libomega.so host side: the batch launch path -- omega_process_frames down to launch_batch, with the
-// meter segments, the counters and the stream layout -- and the meter, true-peak and weighting entry
-// points that share its state. The per-step path is whole in this translation unit, but for the grid
-// arithmetic: batch_plan.hpp's plan_batch lays out the grid of a call's shape as a pure function, and this
-// file enqueues it. enqueue_frames decides the call's shape once (batch layout, meters in the grid,
-// pipelined, overlapped) and hands the batch to one of three enqueue functions, each with its own
-// launch-failure handling: enqueue_batch_chunks (no meters, or a batch longer than kChunkFrames: meter
-// query kernels), enqueue_batch_direct (this call's meter segment as the grid's last) and
-// enqueue_batch_pipelined (the previous call's segment in the grid, this call's left pending).
+// meter segments and the stream layout -- and the meter, true-peak and weighting entry points that share
+// its state. This file enqueues; the arithmetic is in two pure headers: batch_plan.hpp's plan_batch lays
+// out the grid of a call's shape, and meter_sync.hpp's step functions give every counter target of a
+// transition and the ledger (omega_ctx::ms) it leaves, on success and on a failed launch. enqueue_frames
+// decides the call's shape once (batch layout, meters in the grid, pipelined, overlapped) and hands the
+// batch to one of three enqueue functions: enqueue_batch_chunks (no meters, or a batch longer than
+// kChunkFrames: meter query kernels), enqueue_batch_direct (this call's meter segment as the grid's last)
+// and enqueue_batch_pipelined (the previous call's segment in the grid, this call's left pending). Each
+// takes its step, copies the targets into the params, enqueues, and assigns one of the step's ledgers.
 
 #include "batch_plan.hpp"
 #include "host.hpp"
@@ -69,19 +70,26 @@ SpectralParams spectral_params(omega_ctx* c) {
 
 bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
-// Meter aggregates over n_frames x C values, in chunks of at most kChunkFrames frames; each chunk
-// reads the state buffers `cur` and writes `cur ^ 1`.
-std::vector<MeterPrepParams> meter_chunks(omega_ctx* c, const float* lufs, const float* tp, int64_t n_frames,
-                                          double* out) {
+// Meter aggregates over n_frames x C values go in chunks of at most kChunkFrames frames: their frame counts
+std::vector<int64_t> chunk_frames(int64_t n_frames) {
+  std::vector<int64_t> v;
+  for (int64_t f0 = 0; f0 < n_frames; f0 += kChunkFrames) v.push_back(std::min<int64_t>(kChunkFrames, n_frames - f0));
+  return v;
+}
+
+// The params of a step's chunks, consecutive in lufs / tp / out; each reads the state buffers of its
+// parity and writes the other's.
+std::vector<MeterPrepParams> meter_chunks(const omega_ctx* c, const std::vector<ChunkSync>& chunks, const float* lufs,
+                                          const float* tp, double* out) {
   const int C = c->cfg.n_channels;
   std::vector<MeterPrepParams> v;
-  for (int64_t f0 = 0; f0 < n_frames; f0 += kChunkFrames) {
-    const int64_t nf = std::min<int64_t>(kChunkFrames, n_frames - f0);
-    const int a = c->cur, b = c->cur ^ 1;
+  int64_t f0 = 0;
+  for (const ChunkSync& ch : chunks) {
+    const int a = ch.par, b = ch.par ^ 1;
     MeterPrepParams p{};
     p.lufs = lufs + f0 * C;
     p.tp = tp + f0 * C;
-    p.n_frames = nf;
+    p.n_frames = ch.n_frames;
     p.C = C;
     p.hist_l_in = c->d_hist_l[a];
     p.hist_t_in = c->d_hist_t[a];
@@ -114,11 +122,11 @@ std::vector<MeterPrepParams> meter_chunks(omega_ctx* c, const float* lufs, const
     p.gsum = c->d_gsum[a];
     p.out = out + f0 * C * OMEGA_N_METERS;
     p.parts = 3;
-    p.seg_ctr = c->d_kw_done + 4;
-    p.seg_pre_target = c->seg_par[a];
-    p.seg_post_target = c->seg_par[b];
+    p.seg_ctr = c->d_ctr + kCtrSeg;
+    p.seg_pre_target = ch.seg_pre_target;
+    p.seg_post_target = ch.seg_post_target;
     v.push_back(p);
-    c->cur = b;
+    f0 += ch.n_frames;
   }
   return v;
 }
@@ -128,7 +136,9 @@ std::vector<MeterPrepParams> meter_chunks(omega_ctx* c, const float* lufs, const
 int meters_enqueue(omega_ctx* c, const float* lufs, const float* tp, int64_t n_frames, double* out,
                    hipStream_t stream, hipEvent_t tp_ready, unsigned* wait_ctr = nullptr, unsigned wait_target = 0) {
   bool first = true;
-  for (MeterPrepParams p : meter_chunks(c, lufs, tp, n_frames, out)) {
+  const SyncStep st = step_state_chunks(c->ms, chunk_frames(n_frames));
+  c->ms = st.ok;
+  for (MeterPrepParams p : meter_chunks(c, st.chunks, lufs, tp, out)) {
     // (wait_ctr: the first chunk's prep polls it before reading the batch's values -- the true peaks
     // of omega_calculate_lufs on the side stream counting in, instead of an event join)
     if (first && wait_ctr) {
@@ -163,16 +173,17 @@ namespace omega_host __attribute__((visibility("hidden"))) {
 int flush_meters(omega_ctx* c, hipStream_t on) {
   if (!on)
     if (int e = join_batches(c)) return e;
-  if (!c->pend) return 0;
+  if (!c->ms.pend) return 0;
   HIPC(c, hipSetDevice(c->device));
+  const SyncStep st = step_flush(c->ms);
   SpectralParams sp{};
   KWeightParams kp{};
-  const hipError_t le =
-      launch_batch(sp, kp, plan_segment_only(c->pend_nq), c->pend_mq, c->pend_nq, on ? on : c->stream);
-  if (le != hipSuccess) return fail(c, OMEGA_EHIP, "meter segment launch: %s", hipGetErrorString(le));
-  c->pend = false;
-  c->seg_par[c->pend_par] = c->seg_issued + (unsigned)c->pend_nq;
-  c->seg_issued += (unsigned)c->pend_nq;
+  const hipError_t le = launch_batch(sp, kp, plan_segment_only(st.q_n), c->pend_mq, st.q_n, on ? on : c->stream);
+  if (le != hipSuccess) {
+    c->ms = st.fail;
+    return fail(c, OMEGA_EHIP, "meter segment launch: %s", hipGetErrorString(le));
+  }
+  c->ms = st.ok;
   return 0;
 }
 }  // namespace omega_host
@@ -188,7 +199,6 @@ int tail_init(omega_ctx* c) {
   c->tail_ok = -1;
   if (ok && hipExtMallocWithFlags(reinterpret_cast<void**>(&c->d_tail), 8, hipMallocSignalMemory) == hipSuccess) {
     HIPC(c, hipMemset(c->d_tail, 0, 8));
-    c->tail_issued = 0;
     c->tail_ok = 1;
   }
   return 0;
@@ -264,41 +274,42 @@ int enqueue_batch_chunks(omega_ctx* c, const SpectralParams& sp, KWeightParams k
   BatchPlan bp{};
   int grid = 0;
   if (int e = plan_or_fail(c, sh, &bp, &grid)) return e;
-  std::vector<MeterPrepParams> mc;
+  // (no meters: no chunk, and the ledger stays)
+  const SyncStep st = meters ? step_chunks(c->ms, sp.n_cf, sp.C, chunk_frames(n_frames)) : step_state_chunks(c->ms, {});
+  const std::vector<MeterPrepParams> mc = meter_chunks(c, st.chunks, lufs, tp, meters);
   if (meters) {
-    mc = meter_chunks(c, lufs, tp, n_frames, meters);
-    kp.kw_done = c->d_kw_done;
-    c->kw_issued += (unsigned)sp.n_cf;
+    kp.kw_done = c->d_ctr + kCtrKw;
     for (size_t i = 0; i < mc.size(); ++i) {
       MeterPrepParams p = mc[i];
       if (i == 0) {
-        p.wait_ctr = c->d_kw_done;
-        p.wait_target = c->kw_issued;
+        p.wait_ctr = c->d_ctr + kCtrKw;
+        p.wait_target = st.wait_target;
       }
       HIPC(c, launch_meter_prep(p, c->fork[0]));
       c->side_meters = true;
       p.parts = 1;
-      p.q_done = c->d_kw_done + 1;
+      p.q_done = c->d_ctr + kCtrQuery;
       HIPC(c, launch_meter_query(p, c->fork[0]));
       c->side_meters = true;
-      c->q_issued += (unsigned)(((p.n_frames + 3) / 4) * p.C);  // (counted once it is enqueued)
     }
   }
   if (grid > 0) {
     const hipError_t le = launch_batch(sp, kp, bp, MeterPrepParams{}, grid, s);
     if (le != hipSuccess) {
+      c->ms = st.fail;
       // the prep kernel already waits for this batch's count: publish it, so that it (and every later
       // call's target) stays in step with the device counter instead of timing out
-      if (meters) (void)hipMemcpy(c->d_kw_done, &c->kw_issued, sizeof(unsigned), hipMemcpyHostToDevice);
+      if (meters) (void)hipMemcpy(c->d_ctr + kCtrKw, &c->ms.kw, sizeof(unsigned), hipMemcpyHostToDevice);
       return fail(c, OMEGA_EHIP, "batch launch: %s", hipGetErrorString(le));
     }
   }
+  c->ms = st.ok;
   for (size_t i = 0; i < mc.size(); ++i) {
     MeterPrepParams p = mc[i];
     p.parts = 2;
     if (i + 1 == mc.size()) {
-      p.join_ctr = c->d_kw_done + 1;
-      p.join_target = c->q_issued;
+      p.join_ctr = c->d_ctr + kCtrQuery;
+      p.join_target = st.join_target;
     }
     HIPC(c, launch_meter_query(p, s));
   }
@@ -311,44 +322,38 @@ int enqueue_batch_chunks(omega_ctx* c, const SpectralParams& sp, KWeightParams k
 // must be resident while the batch runs (its segment waits for it).
 int enqueue_batch_direct(omega_ctx* c, SpectralParams sp, KWeightParams kp, BatchShape sh, int64_t n_frames,
                          const float* lufs, const float* tp, double* meters, hipStream_t s) {
-  const int64_t n = sp.n_cf;
-  const int n_mq = meter_segment_wgs(n);
-  sh.q_n = n_mq;
+  const SyncStep st = step_direct(c->ms, sp.n_cf, sp.C);
+  sh.q_n = st.q_n;
   sh.q_before_multi = false;
   BatchPlan bp{};
   int grid = 0;
   if (int e = plan_or_fail(c, sh, &bp, &grid)) return e;
-  const int a = c->cur;  // (meter_chunks flips the state parity)
-  const MeterPrepParams m0 = meter_chunks(c, lufs, tp, n_frames, meters)[0];
+  const MeterPrepParams m0 = meter_chunks(c, st.chunks, lufs, tp, meters)[0];
   // the prep on the side stream, waiting for this batch's K-weighting count
   MeterPrepParams p = m0;
-  p.q_done = c->d_kw_done + 3;
-  kp.kw_done = c->d_kw_done;
-  c->kw_issued += (unsigned)n;
-  p.wait_ctr = c->d_kw_done;
-  p.wait_target = c->kw_issued;
+  p.q_done = c->d_ctr + kCtrPrep;
+  kp.kw_done = c->d_ctr + kCtrKw;
+  p.wait_ctr = c->d_ctr + kCtrKw;
+  p.wait_target = st.wait_target;
   HIPC(c, launch_meter_prep(p, c->fork[0]));
   c->side_meters = true;
   MeterPrepParams mq = m0;
-  mq.start_ctr = c->d_kw_done + 3;
-  mq.start_target = c->prep_issued + (unsigned)p.C;
+  mq.start_ctr = c->d_ctr + kCtrPrep;
+  mq.start_target = st.start_target;
   // the meter segment's wait for the true peaks (each true-peak workgroup stores its value write-through
   // and counts in)
-  sp.tp_done = c->d_kw_done + 2;
-  mq.join_ctr = c->d_kw_done + 2;
-  mq.join_target = c->tp_issued + (unsigned)n;
+  sp.tp_done = c->d_ctr + kCtrTp;
+  mq.join_ctr = c->d_ctr + kCtrTp;
+  mq.join_target = st.join_target;
   const hipError_t le = launch_batch(sp, kp, bp, mq, grid, s);
   if (le != hipSuccess) {
+    c->ms = st.fail;
     // the prep kernel already waits for this batch's count: publish it, so that it (and every later
     // call's target) stays in step with the device counter instead of timing out
-    (void)hipMemcpy(c->d_kw_done, &c->kw_issued, sizeof(unsigned), hipMemcpyHostToDevice);
-    c->prep_issued += (unsigned)p.C;
+    (void)hipMemcpy(c->d_ctr + kCtrKw, &c->ms.kw, sizeof(unsigned), hipMemcpyHostToDevice);
     return fail(c, OMEGA_EHIP, "batch launch: %s", hipGetErrorString(le));
   }
-  c->tp_issued += (unsigned)n;
-  c->prep_issued += (unsigned)p.C;
-  c->seg_par[a] = c->seg_issued + (unsigned)n_mq;
-  c->seg_issued += (unsigned)n_mq;
+  c->ms = st.ok;
   return 0;
 }
 
@@ -362,62 +367,52 @@ int enqueue_batch_direct(omega_ctx* c, SpectralParams sp, KWeightParams kp, Batc
 // enqueue_frames launches each call's segment behind its batch).
 int enqueue_batch_pipelined(omega_ctx* c, const SpectralParams& sp, KWeightParams kp, BatchShape sh,
                             int64_t n_frames, const float* lufs, const float* tp, double* meters, hipStream_t s) {
-  sh.q_n = c->pend ? c->pend_nq : 0;
-  sh.q_before_multi = true;
-  BatchPlan bp{};
-  int grid = 0;
-  if (int e = plan_or_fail(c, sh, &bp, &grid)) return e;
-  const int a = c->cur;  // (meter_chunks flips the state parity)
-  const unsigned seg_par_was = c->seg_par[a ^ 1];
-  // the pending segment (parity a ^ 1) is enqueued by this launch: the prep's target for the state it
-  // reads (meter_chunks) counts it
-  if (c->pend) c->seg_par[c->pend_par] = c->seg_issued + (unsigned)c->pend_nq;
-  const MeterPrepParams m0 = meter_chunks(c, lufs, tp, n_frames, meters)[0];
-  MeterPrepParams p = m0;
-  p.q_done = c->d_kw_done + 3;
+  // first use: the mirror words and the tail word
   const size_t mir_n = (size_t)kChunkFrames * c->cfg.n_channels;
   if (!c->d_mirror) {
     HIPC(c, hipMalloc(&c->d_mirror, 2 * mir_n * sizeof(unsigned long long)));
     HIPC(c, hipMemset(c->d_mirror, 0, 2 * mir_n * sizeof(unsigned long long)));
   }
+  if (int e = tail_init(c)) return e;
+  const bool tail = c->tail_ok > 0;
+  const SyncStep st = step_pipelined(c->ms, sp.n_cf, sp.C, tail);
+  sh.q_n = st.q_n;
+  sh.q_before_multi = true;
+  BatchPlan bp{};
+  int grid = 0;
+  if (int e = plan_or_fail(c, sh, &bp, &grid)) return e;
+  const MeterPrepParams m0 = meter_chunks(c, st.chunks, lufs, tp, meters)[0];
+  MeterPrepParams p = m0;
+  p.q_done = c->d_ctr + kCtrPrep;
   // consecutive launches alternate parity: a prep still reading one parity while the next launch's
   // K-weighting writes the other (it waits for nothing), and done before the launch after that
   // (whose predecessor's segment waits for it)
-  const unsigned gen_was = c->mirror_gen;
-  c->mirror_gen = c->mirror_gen == 0xFFFFFFFFu ? 2u : c->mirror_gen + 1;
-  kp.lufs_mirror = c->d_mirror + (c->mirror_gen & 1) * mir_n;
-  kp.mirror_gen = c->mirror_gen;
+  kp.lufs_mirror = c->d_mirror + (st.mirror_gen & 1) * mir_n;
+  kp.mirror_gen = st.mirror_gen;
   p.lufs_mirror = kp.lufs_mirror;
-  p.mirror_gen = c->mirror_gen;
-  if (int e = tail_init(c)) return e;
-  const bool tail = c->tail_ok > 0;
+  p.mirror_gen = st.mirror_gen;
   if (tail) bp.tail_ctr = c->d_tail;
   c->side_meters = true;
   // this call's segment, for the launch that runs it: it starts once the prep has counted in (its batch
   // has ended by then: no wait for the true peaks)
   MeterPrepParams mq = m0;
-  mq.start_ctr = c->d_kw_done + 3;
-  mq.start_target = c->prep_issued + (unsigned)p.C;
+  mq.start_ctr = c->d_ctr + kCtrPrep;
+  mq.start_target = st.start_target;
   const hipError_t le = launch_batch(sp, kp, bp, c->pend_mq, grid, s);
   if (le != hipSuccess) {
-    // (no prep waits for this launch: nothing was enqueued; the generation goes back so the next
-    // launch takes the other parity)
-    c->mirror_gen = gen_was;
-    c->seg_par[a ^ 1] = seg_par_was;  // (the pending segment stays pending)
-    c->cur = a;                       // (no prep writes the other parity's state)
+    // (no prep waits for this launch: nothing was enqueued, the pending segment stays pending and the
+    // next launch takes this one's generation and parities)
+    c->ms = st.fail;
     return fail(c, OMEGA_EHIP, "batch launch: %s", hipGetErrorString(le));
   }
+  c->ms = st.launched;
   if (tail) {
-    HIPC(c, hipStreamWaitValue32(c->fork[0], c->d_tail, c->tail_issued + 1, hipStreamWaitValueGte, 0xFFFFFFFFu));
-    ++c->tail_issued;
+    HIPC(c, hipStreamWaitValue32(c->fork[0], c->d_tail, st.tail_target, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    c->ms = st.waited;
   }
   HIPC(c, launch_meter_prep(p, c->fork[0]));
-  c->prep_issued += (unsigned)p.C;
-  if (c->pend) c->seg_issued += (unsigned)c->pend_nq;
-  c->pend = true;
+  c->ms = st.ok;
   c->pend_mq = mq;
-  c->pend_nq = meter_segment_wgs(sp.n_cf);
-  c->pend_par = a;
   return 0;
 }
 
@@ -445,7 +440,7 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
   if (fold && c->bs[0])
     if (int e = tail_init(c)) return e;
   const bool ovl = fold && c->bs[0] && c->tail_ok > 0;
-  if ((c->pend && (!fold || ovl)) || (c->unjoined && !ovl))
+  if ((c->ms.pend && (!fold || ovl)) || (c->unjoined && !ovl))
     if (int e = flush_meters(c)) return e;
   if (fold && lufs_st && tp_st) {
     // the segment and the prep read the staging slots; the caller's buffers get copies
@@ -468,8 +463,8 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
     // the gate: batch i starts placing workgroups once batch i - 1 has none left to place (its
     // last-dispatched workgroup has bumped the tail count) and fills the slots its drain frees. The
     // wait follows the launch it waits for (the previous call's): shared hardware queues serialise
-    if (c->tail_issued)
-      HIPC(c, hipStreamWaitValue32(b, c->d_tail, c->tail_issued, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    if (c->ms.tail)
+      HIPC(c, hipStreamWaitValue32(b, c->d_tail, c->ms.tail, hipStreamWaitValueGte, 0xFFFFFFFFu));
     const int err = [&]() -> int {
       if (int e = enqueue_batch_pipelined(c, sp, kp, sh, n_frames, lufs, tp, meters, b)) return e;
       // this call's meter segment, a launch of its own behind its batch: it polls the prep's count (the
@@ -505,7 +500,10 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
   if (do_kw) HIPC(c, launch_kweight(W, kp, s));
   std::vector<MeterPrepParams> mc;
   if (meters) {
-    mc = meter_chunks(c, lufs, tp, n_frames, meters);
+    const SyncStep st = step_state_chunks(c->ms, chunk_frames(n_frames));
+    // (a graph capture runs nothing: omega_process_frames takes the same step at each replay)
+    if (!(c->cap && s == c->cap)) c->ms = st.ok;
+    mc = meter_chunks(c, st.chunks, lufs, tp, meters);
     HIPC(c, hipEventRecord(c->ev_kw, s));
     HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_kw, 0));
     for (MeterPrepParams p : mc) {
@@ -655,13 +653,12 @@ int omega_process_frames(omega_ctx* c, const float* x, int64_t n_frames, int64_t
     const std::vector<uint64_t> key = {(uint64_t)dx, (uint64_t)n_frames, (uint64_t)frame_stride,
                                        (uint64_t)channel_stride, (uint64_t)comb, (uint64_t)lufs, (uint64_t)tp,
                                        (uint64_t)meters, (uint64_t)weighted, (uint64_t)mags[0], (uint64_t)mags[1],
-                                       (uint64_t)mags[2], (uint64_t)mags[3], (uint64_t)c->cur};
+                                       (uint64_t)mags[2], (uint64_t)mags[3], (uint64_t)c->ms.cur};
     hipGraphExec_t exec = nullptr;
     for (auto& g : c->graphs)
       if (g.key == key) exec = g.exec;
     if (!exec) {
       if (c->graphs.size() >= 16) drop_graphs(c);
-      const int cur0 = c->cur;
       if (!c->cap) HIPC(c, hipStreamCreateWithFlags(&c->cap, hipStreamNonBlocking));
       HIPC(c, hipStreamBeginCapture(c->cap, hipStreamCaptureModeThreadLocal));
       e = enqueue_frames(c, sp, kp, W, n_frames, lufs, tp, meters, c->cap);
@@ -671,10 +668,9 @@ int omega_process_frames(omega_ctx* c, const float* x, int64_t n_frames, int64_t
       if (ce != hipSuccess) return fail(c, OMEGA_EHIP, "graph capture: %s", hipGetErrorString(ce));
       HIPC(c, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
       c->graphs.push_back({key, graph, exec});
-      c->cur = cur0;  // capture advanced the parity; the replay below advances it for real
     }
     HIPC(c, hipGraphLaunch(exec, c->stream));
-    if (meters) c->cur ^= (int)(((n_frames + kChunkFrames - 1) / kChunkFrames) & 1);
+    if (meters) c->ms = step_state_chunks(c->ms, chunk_frames(n_frames)).ok;  // (the captured call's step)
     return 0;
   }
   // overlapped pipelined calls: what this call reads ([0]) and writes; one that touches what the call
@@ -712,7 +708,7 @@ int omega_process_frames(omega_ctx* c, const float* x, int64_t n_frames, int64_t
 
 int omega_flush_meters(omega_ctx* c) try {
   if (!c) return OMEGA_EINVAL;
-  if (!c->pend && !c->unjoined) return 0;
+  if (!c->ms.pend && !c->unjoined) return 0;
   HIPC(c, hipSetDevice(c->device));
   return flush_meters(c);
 } catch (...) {
@@ -1015,7 +1011,7 @@ int omega_meter_load_history(omega_ctx* c, const float* lufs_inst, int64_t n_l, 
   // as omega_meter_update: after the side stream's last writes of the state, and before its next reads
   HIPC(c, hipEventRecord(c->ev_join[1], c->fork[0]));
   HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[1], 0));
-  const int a = c->cur;
+  const int a = c->ms.cur;
   MeterLoadParams p{dl, dt, (int)n_l, (int)n_t, C, c->HL, c->HT, (float)c->cfg.gate_lufs, c->d_hist_l[a],
                     c->d_hist_t[a], c->d_nl[a], c->d_nt[a], c->d_skeys[a], c->d_ns[a], c->d_t0[a]};
   HIPC(c, launch_meter_load(p, c->stream));
@@ -1068,13 +1064,14 @@ int omega_calculate_lufs(omega_ctx* c, const float* x, int64_t n_frames, int32_t
   {
     const hipStream_t main = c->stream;
     c->stream = c->fork[0];
-    c->tp_count_to = counted ? c->d_kw_done + 5 : nullptr;
+    c->tp_count_to = counted ? c->d_ctr + kCtrLufsTp : nullptr;
     e = omega_true_peak_os(c, dx, ncf, m, oversampling, dt, OMEGA_MEM_DEVICE);
     c->tp_count_to = nullptr;
     c->stream = main;
     if (e) return e;
   }
-  if (counted) c->lt_issued += (unsigned)ncf;
+  const SyncStep st = step_lufs_tp(c->ms, ncf);
+  if (counted) c->ms = st.ok;
   if ((e = omega_weighting(c, dx, ncf, m, mode, nullptr, dl, OMEGA_MEM_DEVICE))) return e;
   if (!counted) {
     // the side stream's last work is the true peak, behind any earlier meter prep: one join serves
@@ -1086,8 +1083,8 @@ int omega_calculate_lufs(omega_ctx* c, const float* x, int64_t n_frames, int32_t
   // for a host-memory call the side stream is ordered after the copies back (no event between the
   // aggregates and the copies)
   const bool host = mem == OMEGA_MEM_HOST;
-  if ((e = meter_update_dev(c, dl, dt, n_frames, dm, false, !host, counted ? c->d_kw_done + 5 : nullptr,
-                            c->lt_issued)))
+  if ((e = meter_update_dev(c, dl, dt, n_frames, dm, false, !host, counted ? c->d_ctr + kCtrLufsTp : nullptr,
+                            st.wait_target)))
     return e;
   if (host) {
     if ((e = h.finish())) return e;

@@ -284,7 +284,7 @@ int build_meter_state(omega_ctx* c) {
     if (!e) e = dalloc(c, &c->d_gcount[b], (size_t)C * (kMeterSeqCap + 1));
     if (!e) e = dalloc(c, &c->d_gsum[b], (size_t)C * (kMeterSeqCap + 1));
   }
-  if (!e) e = dalloc(c, &c->d_kw_done, 8);
+  if (!e) e = dalloc(c, &c->d_ctr, kCtrWords);
   if (e) return e;
   if (!c->h_err) {
     HIPC(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_err), 2 * sizeof(unsigned),
@@ -292,10 +292,8 @@ int build_meter_state(omega_ctx* c) {
     c->h_err[0] = c->h_err[1] = 0;
     HIPC(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_err), c->h_err, 0));
   }
-  HIPC(c, hipMemset(c->d_kw_done, 0, 8 * sizeof(unsigned)));
-  c->kw_issued = c->q_issued = c->tp_issued = c->prep_issued = c->seg_issued = c->lt_issued = 0;
-  c->seg_par[0] = c->seg_par[1] = 0;
-  c->pend = false;
+  HIPC(c, hipMemset(c->d_ctr, 0, kCtrWords * sizeof(unsigned)));
+  c->ms = MeterSync{};
   return omega_meter_reset(c);
 }
 
@@ -496,7 +494,7 @@ int omega_create(const omega_config* cfg, int device, omega_ctx** out) try {
 void omega_destroy(omega_ctx* c) try {
   if (!c) return;
   if (c->device >= 0) (void)hipSetDevice(c->device);
-  if ((c->pend || c->unjoined) && !flush_meters(c)) (void)hipStreamSynchronize(c->stream);  // (the last call's meters)
+  if ((c->ms.pend || c->unjoined) && !flush_meters(c)) (void)hipStreamSynchronize(c->stream);  // (the last call's meters)
   for (hipStream_t st : c->bs)
     if (st) (void)hipStreamSynchronize(st);
   if (c->own) (void)hipStreamSynchronize(c->own);
@@ -534,7 +532,7 @@ int omega_set_stream(omega_ctx* c, void* s) try {
   if (!c) return OMEGA_EINVAL;
   const hipStream_t ns = static_cast<hipStream_t>(s);  // NULL = the null (default) stream, e.g. torch's
   if (ns != c->stream) {
-    if (c->pend || c->unjoined) {  // (a pending meter segment runs on its batch's stream)
+    if (c->ms.pend || c->unjoined) {  // (a pending meter segment runs on its batch's stream)
       HIPC(c, hipSetDevice(c->device));
       if (int e = flush_meters(c)) return e;
     }
@@ -558,7 +556,7 @@ int omega_set_stream(omega_ctx* c, void* s) try {
 int omega_check_queues(omega_ctx* c, int* shared) try {
   if (!c) return OMEGA_EINVAL;
   HIPC(c, hipSetDevice(c->device));
-  if (c->pend || c->unjoined) {  // (the probe synchronises the streams; a pending segment launches first)
+  if (c->ms.pend || c->unjoined) {  // (the probe synchronises the streams; a pending segment launches first)
     if (int e = flush_meters(c)) return e;
   }
   if (int e = side_stream_check(c, true)) return e;
@@ -579,7 +577,7 @@ int omega_get_config(const omega_ctx* c, omega_config* cfg, int* device) {
 
 int omega_set_graphs(omega_ctx* c, int enable) try {
   if (!c) return OMEGA_EINVAL;
-  if (c->pend || c->unjoined) {
+  if (c->ms.pend || c->unjoined) {
     HIPC(c, hipSetDevice(c->device));
     if (int e = flush_meters(c)) return e;
   }
@@ -595,7 +593,7 @@ int omega_set_graphs(omega_ctx* c, int enable) try {
 
 int omega_synchronize(omega_ctx* c) try {
   if (!c) return OMEGA_EINVAL;
-  if (c->pend || c->unjoined) {
+  if (c->ms.pend || c->unjoined) {
     HIPC(c, hipSetDevice(c->device));
     if (int e = flush_meters(c)) return e;
   }
@@ -607,7 +605,7 @@ int omega_synchronize(omega_ctx* c) try {
 
 int omega_set_meter_pipelining(omega_ctx* c, int enable) try {
   if (!c) return OMEGA_EINVAL;
-  if (!enable && (c->pend || c->unjoined)) {
+  if (!enable && (c->ms.pend || c->unjoined)) {
     HIPC(c, hipSetDevice(c->device));
     if (int e = flush_meters(c)) return e;
   }

@@ -21,6 +21,7 @@
 #include "../../include/omega.h"
 #include "batch_plan.hpp"
 #include "design.hpp"
+#include "meter_sync.hpp"
 #include "params.hpp"
 
 namespace omega {
@@ -262,38 +263,21 @@ struct omega_ctx {
   // graph capture, or omega_set_graphs layout bits) the full-chip kernels back to back with the meter
   // aggregates on a side stream joined by events.
   int layout = 3;
-  unsigned* d_kw_done = nullptr;  // batch_kernel's K-weighting workgroups count themselves in here
-  unsigned kw_issued = 0;         // K-weighting workgroups launched with the count on (wraps)
-  unsigned q_issued = 0;          // LUFS-meter query workgroups launched with the count on (d_kw_done[1])
-  unsigned tp_issued = 0;         // batch true-peak workgroups launched with the count on (d_kw_done[2])
-  unsigned prep_issued = 0;       // meter prep workgroups launched with the count on (d_kw_done[3])
-  unsigned seg_issued = 0;        // meter-segment workgroups launched (they count in at d_kw_done[4])
-  unsigned lt_issued = 0;         // omega_calculate_lufs true-peak workgroups (they count in at d_kw_done[5])
+  // the device counter words (meter_sync.hpp: MeterCounter) and the host's ledger of what was launched to
+  // count into them; every transition is a step function there, the table is in DESIGN.md §4
+  unsigned* d_ctr = nullptr;
+  MeterSync ms;
   unsigned* tp_count_to = nullptr;  // set inside omega_calculate_lufs: its true peaks count in here
   bool side_meters = false;  // meter kernels enqueued on fork[0] since omega_calculate_lufs last joined it
-  // seg_issued once the last meter segment that reads parity p's scratch / state has counted in: the
-  // preps' targets before they overwrite them (MeterPrepParams::seg_ctr)
-  unsigned seg_par[2] = {0, 0};
-  // meter pipelining (omega_set_meter_pipelining): the meter segment of the last default-layout batch
-  // with meters, not yet launched -- the next such batch launch runs it first in its grid, any other
-  // use of the meter state (and omega_synchronize / omega_flush_meters) launches it on its own.
-  // (Where batches overlap -- bs below -- each call launches its own segment behind its batch on the
-  // batch's stream and nothing stays pending: `unjoined` takes the place of `pend`.)
+  // meter pipelining (omega_set_meter_pipelining): the params of the pending segment (MeterSync::pend)
   bool pipe = false;
-  bool pend = false;
   MeterPrepParams pend_mq{};
-  int pend_nq = 0, pend_par = 0;
   int stage_par = 0;  // pipelined calls alternate the staging of LUFS_inst / TP (the segment reads them later)
-  // pipelined launches: the grid's last-dispatched workgroup counts in here (signal memory, so the side
-  // stream's command processor can wait on it: hipStreamWaitValue32) -- the prep is dispatched only
-  // once the batch has no workgroup left to place, into the slots its tail leaves idle, instead of
-  // holding a CU through the batch (step 66.5-67.1 vs 67.2-67.9 us); -1: not supported, no wait
+  // pipelined launches: the signal-memory word the grid's last-dispatched workgroup bumps, for the side
+  // stream's hipStreamWaitValue32 before the prep (tail_ok: 1 ready, -1 not supported, no wait), and the
+  // K-weighting workgroups' {generation, LUFS} words, two parities of kMeterChunk x C
   unsigned* d_tail = nullptr;
-  unsigned tail_issued = 0;
-  // (meter pipelining) the K-weighting workgroups' {generation, LUFS} words, two parities of
-  // kChunkFrames x C (KWeightParams::lufs_mirror)
   unsigned long long* d_mirror = nullptr;
-  unsigned mirror_gen = 0;
   int tail_ok = 0;
   // overlapped pipelined batches (omega_set_meter_pipelining, with tail_ok > 0): call i's batch launch
   // and, behind it, its meter segment as a launch of its own go to bs[i & 1] (two non-blocking streams,
@@ -390,11 +374,10 @@ struct omega_ctx {
   float* d_hist_t[2] = {};
   int* d_nl[2] = {};
   int* d_nt[2] = {};
-  int cur = 0;
   unsigned long long* d_skeys[2] = {};  // sorted gated history keys (double-buffered state)
   int* d_ns[2] = {};
   uint32_t* d_t0[2] = {};
-  // per-batch meter scratch, two sets by the state's parity (cur): the next batch's prep writes the
+  // per-batch meter scratch, two sets by the state's parity (MeterSync::cur): the next batch's prep writes the
   // other set from before its K-weighting values are in, while this batch's queries read this one
   float* d_core[2] = {nullptr, nullptr};
   MeterExt* d_ext[2] = {nullptr, nullptr};

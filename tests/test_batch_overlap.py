@@ -131,6 +131,36 @@ def test_input_lifetime_with_dropped_temporaries():
         assert torch.equal(m.cpu(), r["meters"]), i
 
 
+def test_one_context_through_every_meter_path():
+    """One context through every path of the meter ledger (csrc/meter_sync.hpp) in one sequence: a direct
+    batch (its own segment in the grid), pipelining switched on, a pipelined batch (its segment left
+    pending), omega_calculate_lufs over 4 frames of 2048 samples (another entry point: it flushes the
+    pending segment, and its counted true peaks release its prep) and a pipelined batch again. Every
+    output, the host-memory call's included, is bitwise the unpipelined context's over the same calls."""
+    import torch
+    sizes = (4, 8, 4)
+    x = torch.cat(_batches())[:sum(sizes) + 4]
+    short = x[sum(sizes):, :, :2048].reshape(8, 2048).cpu().numpy()
+    res = []
+    for pipe in (False, True):
+        eng = _engine(False)
+        outs = [eng.process_frames(x[:4].contiguous(), 4, 2 * W, W, meters=True)]
+        eng.set_meter_pipelining(pipe)
+        outs.append(eng.process_frames(x[4:12].contiguous(), 8, 2 * W, W, meters=True))
+        li, tp, met = eng.calculate_lufs(short)
+        outs.append({"lufs_inst": torch.from_numpy(li), "true_peak_db": torch.from_numpy(tp),
+                     "meters": torch.from_numpy(met)})
+        outs.append(eng.process_frames(x[12:16].contiguous(), 4, 2 * W, W, meters=True))
+        eng.synchronize()
+        torch.cuda.synchronize()
+        res.append([{k: o[k].cpu() for k in KEYS if k in o} for o in outs])
+        eng.close()
+    for i, (a, b) in enumerate(zip(*res)):
+        assert a.keys() == b.keys() and "meters" in a
+        for k in a:
+            assert torch.equal(a[k], b[k]), (i, k)  # (equal: no NaN either)
+
+
 def test_fallback_output_over_previous_input():
     """The second call's `combined` is a view of the first call's input storage: the calls run serial."""
     import torch

@@ -8,7 +8,6 @@ program runs decode_block, the composition of the pieces the kernel decodes a bl
 of every planned grid, and what it returns must be the model's work for that block."""
 import itertools
 import os
-import shutil
 import subprocess
 import sys
 
@@ -16,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import REPO
+from host_program import compile_host_program
 
 sys.path.insert(0, os.path.join(REPO, "tools", "model"))
 import batch_plan_model as M  # noqa: E402
@@ -60,24 +60,7 @@ def _line(case):
 def dump(tmp_path_factory):
     """The program, compiled once: the host compiler against the ROCm headers, or hipcc (a .cpp file is host
     code to it) where g++ is missing or cannot digest them."""
-    exe = str(tmp_path_factory.mktemp("batch_plan") / "batch_plan_dump")
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    rocm = os.environ.get("ROCM_PATH") or os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
-    tried = []
-    if shutil.which("g++") and os.path.exists(os.path.join(rocm, "include", "hip", "hip_runtime.h")):
-        tried.append(["g++", "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", f"-I{rocm}/include", "-o", exe, SRC])
-    if os.path.exists(hipcc):
-        tried.append([hipcc, "-std=c++17", "-O1", "-o", exe, SRC])
-    if not tried:
-        pytest.skip("neither g++ with the ROCm headers nor hipcc available")
-    errs = []
-    for cmd in tried:
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        errs.append(" ".join(cmd) + "\n" + r.stderr[-2000:])
-    else:
-        pytest.fail("batch_plan_dump.cpp does not compile:\n" + "\n".join(errs))
+    exe = compile_host_program(SRC, str(tmp_path_factory.mktemp("batch_plan") / "batch_plan_dump"))
 
     def run(lines):
         r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
