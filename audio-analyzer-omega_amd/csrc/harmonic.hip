@@ -8,7 +8,7 @@
 //     :199-203  scipy.signal.find_peaks(height = 0.1 max, distance = 10): plateau-aware local maxima
 //               (the middle (left + right) // 2 of a flat top whose two sides fall), the float32 height
 //               threshold, then scipy's distance rule over ALL peaks, highest first, in the parallel form
-//               of pitch.hip (an undecided peak that no undecided peak within 9 bins exceeds is kept and
+//               of peaks.hpp (an undecided peak that no undecided peak within 9 bins exceeds is kept and
 //               removes the peaks within 9 bins)
 //     :281-333  one lane per (peak, harmonic) for the surviving peaks with 20 <= f <= 2000: the nearest
 //               bin (np.argmin's first minimum, by bisection of the increasing table and a comparison
@@ -38,10 +38,11 @@
 // own error.
 #include <hip/hip_runtime.h>
 
-#pragma clang fp contract(off)  // (above the project headers: numpy_emul.hpp and wg64.hpp take this state)
+#pragma clang fp contract(off)  // (above the project headers: numpy_emul.hpp, peaks.hpp and wg64.hpp take this state)
 
 #include "numpy_emul.hpp"
 #include "params.hpp"
+#include "peaks.hpp"
 #include "wg64.hpp"
 
 namespace omega {
@@ -149,37 +150,10 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
       const float hmin = __fmul_rn((float)mx, 0.1f);  // np.float32 max x Python float: float32
       int any = 0;
       for (int i = 1 + t; i < K - 1; i += kHT) {
-        const float v = spec[i];
-        if (spec[i - 1] < v) {
-          int j = i + 1;
-          while (j < K - 1 && spec[j] == v) ++j;  // (bounded by the spectrum's end)
-          if (spec[j] < v && v >= hmin) {
-            und[(i + j - 1) >> 1] = 1;
-            any = 1;
-          }
-        }
+        const int pkx = local_max_at(spec, K, i);
+        if (pkx >= 0 && spec[i] >= hmin) und[pkx] = 1, any = 1;  // (spec[i] is the plateau's height)
       }
-      __syncthreads();
-      for (int round = 0; round < K && __syncthreads_or(any); ++round) {
-        for (int i = t; i < K; i += kHT) {
-          if (!und[i]) continue;
-          const float v = spec[i];
-          bool top = true;
-          for (int j = max(0, i - kHmDistance + 1); j < min(K, i + kHmDistance); ++j)
-            if (j != i && und[j] && (spec[j] > v || (spec[j] == v && j > i))) top = false;
-          if (top) kept[i] = 1;
-        }
-        __syncthreads();
-        any = 0;
-        for (int i = t; i < K; i += kHT) {
-          if (!und[i]) continue;
-          bool gone = kept[i] != 0;
-          for (int j = max(0, i - kHmDistance + 1); j < min(K, i + kHmDistance) && !gone; ++j)
-            if (kept[j]) gone = true;
-          if (gone) und[i] = 0;
-          else any = 1;
-        }
-      }
+      select_by_distance<kHT>(spec, und, kept, 0, K, kHmDistance, any);
       // ---- the kept peaks with 20 <= f <= 2000, in ascending order ----
       const int C = (K + kHT - 1) / kHT;
       const int c0 = min(t * C, K), c1 = min(c0 + C, K);

@@ -12,7 +12,7 @@
 //     :293-330  spectral tilt from the low / mid / high sums, the x 1.2 boost above low_ratio > 0.5
 //     :332-384  rap vocals: find_peaks(|spectrum[vocal]|, prominence = float32(max * 0.3), distance = 20):
 //               scipy's local maxima (the middle of a plateau), its distance rule in the parallel form of
-//               pitch.hip, then one lane per surviving peak walks left and right to the next higher
+//               peaks.hpp, then one lane per surviving peak walks left and right to the next higher
 //               sample or the array end for the two minima; prominence and threshold compare in float64
 //   role 1, the audio side (float64 like the reference's scipy path; sosfilt of float32 audio is float64)
 //     :100      rms = np.sqrt(np.mean(x ** 2)) in the audio's precision (float32: bit for bit)
@@ -38,10 +38,11 @@
 // numpy's pairwise order; they agree with it to a few 1e-16 relative, far inside the 1e-9 the filters set.
 #include <hip/hip_runtime.h>
 
-#pragma clang fp contract(off)  // (above the project headers: numpy_emul.hpp and wg64.hpp take this state)
+#pragma clang fp contract(off)  // (above the project headers: numpy_emul.hpp, peaks.hpp and wg64.hpp take this state)
 
 #include "numpy_emul.hpp"
 #include "params.hpp"
+#include "peaks.hpp"
 #include "wg64.hpp"
 
 namespace omega {
@@ -50,16 +51,6 @@ namespace {
 
 constexpr int kHT = kHipHopThreads;
 constexpr int kHhVocalDistance = 20;  // find_peaks(distance=20): a kept peak removes those < 20 bins away
-
-// scipy's _local_maxima_1d at plateau start i (0 < i < n - 1): the peak's index, or -1
-template <class T>
-__device__ __forceinline__ int hh_local_max(const T* x, int n, int i) {
-  const T v = x[i];
-  if (!(x[i - 1] < v)) return -1;
-  int j = i + 1;
-  while (j < n - 1 && x[j] == v) ++j;
-  return x[j] < v ? (i + j - 1) / 2 : -1;
-}
 
 // ---- role 1: the audio side ----
 __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, double* o, unsigned char* smem) {
@@ -206,7 +197,7 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
   for (int i = t; i < m; i += kHT) cand[i] = 0;
   __syncthreads();
   for (int i = 1 + t; i < m - 1; i += kHT) {
-    const int pkx = hh_local_max(S, m, i);
+    const int pkx = local_max_at(S, m, i);
     if (pkx >= 0 && S[pkx] >= thr) cand[pkx] = 1;
   }
   __syncthreads();
@@ -333,43 +324,13 @@ __device__ __forceinline__ void hh_spectrum(const HipHopParams& p, int64_t f, do
     const double pmin = (double)__fmul_rn(vmax, 0.3f);  // np.max(.) * 0.3 is a float32, widened for the comparison
     int any = 0;
     for (int i = 1 + t; i < n - 1; i += kHT) {
-      const int pkx = hh_local_max(v, n, i);
+      const int pkx = local_max_at(v, n, i);
       if (pkx >= 0) und[pkx] = 1, any = 1;
     }
-    __syncthreads();
-    // scipy's _select_by_peak_distance (greedy, descending height) in its parallel form: an undecided
-    // peak that no undecided peak within 19 bins exceeds is kept, and removes the peaks within 19 bins.
-    // The highest undecided peak always qualifies, so every round decides at least one peak.
-    for (int round = 0; round < n && __syncthreads_or(any); ++round) {
-      for (int i = t; i < n; i += kHT) {
-        if (!und[i]) continue;
-        const float h = v[i];
-        bool top = true;
-        for (int j = max(0, i - kHhVocalDistance + 1); j < min(n, i + kHhVocalDistance); ++j)
-          if (j != i && und[j] && (v[j] > h || (v[j] == h && j > i))) top = false;
-        if (top) keep[i] = 1;
-      }
-      __syncthreads();
-      any = 0;
-      for (int i = t; i < n; i += kHT) {
-        if (!und[i]) continue;
-        bool gone = keep[i] != 0;
-        for (int j = max(0, i - kHhVocalDistance + 1); j < min(n, i + kHhVocalDistance) && !gone; ++j)
-          if (keep[j]) gone = true;
-        if (gone) und[i] = 0;
-        else any = 1;
-      }
-    }
-    // scipy's _peak_prominences (no wlen): the minima up to the next higher sample or the array end
-    for (int i = t; i < n; i += kHT) {
-      if (!keep[i]) continue;
-      const float h = v[i];
-      float lmin = h, rmin = h;
-      for (int j = i; j >= 0 && v[j] <= h; --j) lmin = fminf(lmin, v[j]);
-      for (int j = i; j < n && v[j] <= h; ++j) rmin = fminf(rmin, v[j]);
-      const double prom = (double)h - (double)fmaxf(lmin, rmin);
-      if (pmin <= prom) npk += 1.0;
-    }
+    select_by_distance<kHT>(v, und, keep, 0, n, kHhVocalDistance, any);
+    // one lane per surviving peak: its prominence against the threshold, in float64
+    for (int i = t; i < n; i += kHT)
+      if (keep[i] && pmin <= prominence(v, n, i)) npk += 1.0;
     npk = block_sum(npk, red);
   }
   if (t == 0) {

@@ -36,6 +36,7 @@
 #include <hip/hip_runtime.h>
 
 #include "params.hpp"
+#include "peaks.hpp"
 #include "wg64.hpp"
 
 namespace omega {
@@ -202,29 +203,8 @@ __global__ __launch_bounds__(kPT) void pitch_kernel(PitchParams p) {
       kept[i] = 0;
       any |= pk;
     }
-    // scipy's _select_by_peak_distance (greedy, descending height) in its parallel form: an undecided
-    // peak that no undecided peak within 19 lags exceeds is kept, and removes the peaks within 19
-    // lags. The highest undecided peak always qualifies, so every round decides at least one peak.
-    for (int round = 0; round < n && __syncthreads_or(any); ++round) {
-      for (int i = lo + t; i < hi; i += kPT) {
-        if (!und[i]) continue;
-        const double v = buf[i];
-        bool top = true;
-        for (int j = max(lo, i - kPeakDistance + 1); j < min(hi, i + kPeakDistance); ++j)
-          if (j != i && und[j] && (buf[j] > v || (buf[j] == v && j > i))) top = false;
-        if (top) kept[i] = 1;
-      }
-      __syncthreads();
-      any = 0;
-      for (int i = lo + t; i < hi; i += kPT) {
-        if (!und[i]) continue;
-        bool gone = kept[i] != 0;
-        for (int j = max(lo, i - kPeakDistance + 1); j < min(hi, i + kPeakDistance) && !gone; ++j)
-          if (kept[j]) gone = true;
-        if (gone) und[i] = 0;
-        else any = 1;
-      }
-    }
+    // scipy's _select_by_peak_distance over the candidates of [lo, hi), in the parallel form of peaks.hpp
+    select_by_distance<kPT>(buf, und, kept, lo, hi, kPeakDistance, any);
     int first = 0x7fffffff;
     for (int i = lo + t; i < hi; i += kPT)
       if (kept[i]) first = min(first, i);

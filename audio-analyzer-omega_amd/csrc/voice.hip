@@ -27,9 +27,10 @@
 
 #include <algorithm>
 
-#pragma clang fp contract(off)  // (above the project headers: wg64.hpp takes this state)
+#pragma clang fp contract(off)  // (above the project headers: peaks.hpp and wg64.hpp take this state)
 
 #include "params.hpp"
+#include "peaks.hpp"
 #include "wg64.hpp"
 
 namespace omega {
@@ -116,17 +117,8 @@ __device__ __forceinline__ void voice_spectrum(const VoiceParams& p, int64_t f, 
 
   // :98 the local maxima, their prominences, and :101-115 the lowest kept bin of each range
   for (int i = t + 1; i < K - 1; i += kVT) {
-    const float xi = sm[i];
-    if (!(sm[i - 1] < xi)) continue;
-    int ahead = i + 1;
-    while (ahead < K - 1 && sm[ahead] == xi) ++ahead;
-    if (!(sm[ahead] < xi)) continue;
-    const int pk = (i + ahead - 1) / 2;
-    float lmin = xi, rmin = xi;
-    for (int j = pk; j >= 0 && sm[j] <= xi; --j) lmin = fminf(lmin, sm[j]);
-    for (int j = pk; j < K && sm[j] <= xi; ++j) rmin = fminf(rmin, sm[j]);
-    const double prom = (double)xi - (double)fmaxf(lmin, rmin);
-    if (!(prom >= thr) || pk >= p.n_freq) continue;
+    const int pk = local_max_at(sm, K, i);
+    if (pk < 0 || !(prominence(sm, K, pk) >= thr) || pk >= p.n_freq) continue;
     const double fr = (double)pk * p.bin_hz;
     if (200.0 <= fr && fr <= 900.0) atomicMin(&first[0], pk);
     if (800.0 <= fr && fr <= 2500.0) atomicMin(&first[1], pk);

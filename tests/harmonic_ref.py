@@ -230,8 +230,10 @@ def formants_ext(audio, fs):
     return sorted(out)[:4], z
 
 
-def analyze(spec, freqs, audio=None, fs=48000, prev=None, f64=False):
-    """One detect_harmonic_series call. prev: the previous call's spectrum or None."""
+def analyze(spec, freqs, audio=None, fs=48000, prev=None, f64=False, select=None):
+    """One detect_harmonic_series call. prev: the previous call's spectrum or None. select: None for scipy's
+    own distance rule, or select(x, candidates, distance) -> the kept peaks (the rule of
+    tools/model/peaks_model.py, for spectra with equal heights where scipy has no rule of its own)."""
     x = np.asarray(spec, np.float32)
     if f64:
         x = x.astype(np.float64)
@@ -239,6 +241,8 @@ def analyze(spec, freqs, audio=None, fs=48000, prev=None, f64=False):
     freqs = np.asarray(freqs, np.float64)
     nyq = fs / 2
     peaks, _ = sps.find_peaks(x, height=np.max(x) * 0.1, distance=10)
+    if select is not None:  # find_peaks' order: the height condition, then the distance rule
+        peaks = np.asarray(select(x, list(sps.find_peaks(x, height=np.max(x) * 0.1)[0]), 10), np.intp)
     found = []
     for pk in peaks:
         if 20 <= freqs[pk] <= 2000:

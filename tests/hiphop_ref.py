@@ -94,7 +94,9 @@ def band_ranges(freqs, fs):
     return out
 
 
-def spectrum_side(spec, freqs, fs):
+def spectrum_side(spec, freqs, fs, select=None):
+    """select: None for scipy's own distance rule, or select(x, candidates, distance) -> the kept peaks (the
+    rule of tools/model/peaks_model.py, for spectra with equal heights where scipy has no rule of its own)."""
     fft_data = np.asarray(spec, np.float32)
     freqs = np.asarray(freqs, np.float64)
     e = {}
@@ -135,6 +137,9 @@ def spectrum_side(spec, freqs, fs):
         vm = np.abs(fft_data[vocal_mask])
         if len(vm) > 10:
             peaks, _ = scipy_signal.find_peaks(vm, prominence=np.max(vm) * 0.3, distance=20)
+            if select is not None:  # find_peaks' order: the distance rule over all maxima, then the prominences
+                kept = np.asarray(select(vm, list(scipy_signal.find_peaks(vm)[0]), 20), np.intp)
+                peaks = kept[scipy_signal.peak_prominences(vm, kept)[0] >= np.max(vm) * 0.3]
             e["vocal_peaks"] = peaks
             e["vocal_distance_peaks"] = scipy_signal.find_peaks(vm, distance=20)[0]
             e["vocal_pmin"] = float(np.max(vm) * 0.3)

@@ -18,12 +18,17 @@ thd and flux 0, thd_plus_noise <= 3.3e-13, hnr_db <= 1.5e-14 dB, formants <= 2.7
 import ctypes as C
 import functools
 import json
+import os
+import sys
 
 import numpy as np
 import pytest
 
 import harmonic_ref as HR
-from conftest import load_golden
+from conftest import REPO, load_golden
+
+sys.path.insert(0, os.path.join(REPO, "tools", "model"))
+import peaks_model as M  # noqa: E402
 
 GROUPS = ("app", "k1025", "k4097", "m1024", "m4096", "fs44", "pure", "plateau", "distance", "noseries", "offset",
           "silent", "realroot", "seq")
@@ -472,3 +477,28 @@ def test_harmonic_nonfinite_previous_and_window_cache():
             else:
                 np.testing.assert_array_equal(row, first[m])
     check_frame("k1025", 0, first[2048], *[a[0] for a in analyzer("k1025").analyze_frames(spec[None], freqs, audio[None])[1:]])
+
+
+@pytest.mark.gpu
+def test_harmonic_series_with_equal_height_peaks_nine_bins_apart():
+    """One 512-bin spectrum of spikes on a zero floor: a fundamental at bin 28 with its harmonics at 56 and 84,
+    and an equally high peak 9 bins above it at 37 with harmonics at 74 and 111. The distance rule keeps one of
+    the pair: the later one by the kernels' rule, so the series on bin 37 is found and the one on bin 28 is
+    not. The expected series are the restatement's with the kept peaks from tools/model/peaks_model.py (scipy
+    has no rule for equal heights), and they are not the series the opposite tie rule gives."""
+    freqs = np.linspace(0.0, 24000.0, 512)
+    spec = np.zeros(512, np.float32)
+    spec[[28, 56, 84]] = 1.0, 0.8, 0.6
+    spec[[37, 74, 111]] = 1.0, 0.8, 0.6
+
+    def series(later):
+        e = HR.analyze(spec, freqs, None, 48000,
+                       select=lambda x, cand, d: M.select_by_distance(x, cand, d, later_wins=later)[0])
+        return np.concatenate([e["series_peak"][:, None], e["series_bins"]], axis=1)
+    want, other = series(True), series(False)
+    assert list(want[:, 0]) == [37] and list(other[:, 0]) == [28]  # (a series either way, on another peak)
+    assert list(want[0, 1:4]) == [37, 74, 111]
+    out, sb, ss = analyzer("app").analyze_frames(spec[None], freqs, None)
+    assert out[0, 0] == len(want) and out[0, 15] == 0
+    np.testing.assert_array_equal(sb[0, :len(want)], want)
+    assert (sb[0, len(want):] == -1).all() and ss[0, 0] > 0.3 and not ss[0, len(want):].any()

@@ -22,12 +22,17 @@ moves the filtered RMS by at most 2e-12.
 import ctypes as C
 import functools
 import json
+import os
+import sys
 
 import numpy as np
 import pytest
 
 import hiphop_ref as HR
-from conftest import load_golden
+from conftest import REPO, load_golden
+
+sys.path.insert(0, os.path.join(REPO, "tools", "model"))
+import peaks_model as M  # noqa: E402
 
 GROUPS = ("app", "app1025", "m64", "m512", "m8192", "fs44", "fs16", "twopeak", "onepeak", "nopeak", "k16a", "k16b",
           "k16c", "edges", "vocal", "hann", "silent", "lowratio")
@@ -455,3 +460,48 @@ def test_hiphop_reconfigure_rate():
     assert int(b[0][0, COL["kick_peak_count"]]) >= 3
     assert not np.array_equal(a[1][0], b[1][0]) and a[0][0, COL["sub_bass_rms"]] != b[0][0, COL["sub_bass_rms"]]
     assert np.diff(b[1][0][b[1][0] >= 0]).min() >= 1600 > int(0.1 * 16000) - 1
+
+
+def vocal_tie_spectra():
+    """Three 1025-bin spectra whose vocal range (bins 9..128 of the 48 kHz table, 120 bins) holds designed
+    spikes on a zero floor, positions relative to the range's first bin:
+      0  two equal peaks 19 bins apart (10, 29) and a lower one at 45, 16 above the second: the later of the
+         equal pair is kept and removes both others, the earlier one would leave the third standing
+      1  six peaks 19 apart with increasing heights: one is kept and its lower neighbour removed per round
+      2  flat tops of width 2 (30, 31) and 3 (69..71) with lower peaks exactly 20 past their middles (50, 90),
+         which stay only while the middles are 30 and 70"""
+    freqs = np.linspace(0.0, 24000.0, 1025)
+    lo, n = HR.band_ranges(freqs, 48000)[6]
+    assert (lo, n) == (9, 120)
+    spec = np.zeros((3, 1025), np.float32)
+    v = spec[:, lo:lo + n]
+    v[0, [10, 29, 45]] = 1.0, 1.0, 0.8
+    v[1, 5 + 19 * np.arange(6)] = 0.5 + 0.1 * np.arange(6)
+    v[2, [30, 31]], v[2, 50], v[2, 69:72], v[2, 90] = 1.0, 0.6, 0.9, 0.5
+    return freqs, spec
+
+
+@pytest.mark.gpu
+def test_hiphop_vocal_peaks_equal_heights_staircase_and_plateaus():
+    """The vocal peak count (column 7) on designed spectra with equal heights, several rounds of the distance
+    rule and flat tops, at 1025 bins and 64 samples. The expected counts are the restatement's with the kept
+    peaks from tools/model/peaks_model.py ("the later index wins"; scipy has no rule for equal heights), and
+    they are not the counts the opposite tie rule gives."""
+    freqs, spec = vocal_tie_spectra()
+    rounds = []
+
+    def later(x, cand, d):
+        kept, r = M.select_by_distance(x, cand, d)
+        rounds.append(r)
+        return kept
+
+    def earlier(x, cand, d):
+        return M.select_by_distance(x, cand, d, later_wins=False)[0]
+    want = [HR.spectrum_side(s, freqs, 48000, later)["vocal_peak_count"] for s in spec]
+    other = [HR.spectrum_side(s, freqs, 48000, earlier)["vocal_peak_count"] for s in spec]
+    print("expected counts:", want, "with the earlier index winning:", other, "rounds:", rounds)
+    assert want == [1, 3, 4] and other == [2, 3, 4] and rounds[1] == 3  # (non-zero, and the tie rule shows)
+    audio = np.sin(0.3 * np.arange(64), dtype=np.float32)[None].repeat(3, axis=0)
+    out, _ = detector("app").analyze_frames(spec, freqs, audio)
+    assert not out[:, COL["flags"]].any()
+    assert list(out[:, COL["vocal_peak_count"]]) == want
