@@ -86,29 +86,16 @@ int omega_basszoom_configure(omega_ctx* c, const omega_basszoom_config* cfg) try
                 kBzMaxBins, kBzFft);
   HIPC(c, hipSetDevice(c->device));
   BassZoomState& v = c->basszoom;
-  if (!v.tw) {
-    std::vector<double2> t(kBzFft);
-    for (int j = 0; j < kBzFft; ++j)
-      t[j] = make_double2(std::cos(2 * M_PI * j / kBzFft), -std::sin(2 * M_PI * j / kBzFft));
-    if (int e = upload(c, &v.tw, t)) return e;
-  }
   const int nw = std::min(cfg->frame_len, kBzFft);
-  double* win = nullptr;
-  if (int e = cached(v.win, nw, &win, [&](double** d) -> int {
-        std::vector<double> w(nw);
-        for (int i = 0; i < nw; ++i) w[i] = nw == 1 ? 1.0 : np_window(OMEGA_WIN_HANN, nw, i);  // np.hanning(1) is [1.]
-        return upload(c, d, w);
-      }))
-    return e;
   BassZoomParams p{};
+  if (int e = get_twiddles64(c, kBzFft, kBzFft, &p.tw)) return e;
+  if (int e = get_window64(c, OMEGA_WIN_HANN, nw, &p.win)) return e;  // (np.hanning(1) is [1.])
   p.nw = nw;
   p.first_bin = m.first_bin;
   p.n_valid = m.n_valid;
   p.bins_per_bar = m.bins_per_bar;
   p.n_bars = m.n_bars;
   for (int i = 0; i < m.n_bars; ++i) p.comp[i] = m.comp[i];
-  p.win = win;
-  p.tw = v.tw;
   v.p = p;
   v.set = true;
   return 0;

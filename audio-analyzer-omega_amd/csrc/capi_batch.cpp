@@ -17,21 +17,12 @@ namespace {
 constexpr int kChunkFrames = kMeterChunk;
 
 int get_kw_tab(omega_ctx* c, int M, int L, BiquadTab** out) {
-  const auto key = std::make_pair(M, L);
-  auto it = c->kw_tabs.find(key);
-  if (it != c->kw_tabs.end()) {
-    *out = it->second;
-    return 0;
-  }
-  const double fs = c->cfg.sample_rate;
-  std::vector<BiquadTab> t = {make_biquad_tab(butter2(38.0, fs, true), L),
-                              make_biquad_tab(butter2(1500.0, fs, true), L)};
-  BiquadTab* d = nullptr;
-  int r = upload(c, &d, t);
-  if (r) return r;
-  c->kw_tabs[key] = d;
-  *out = d;
-  return 0;
+  return cached(c->kw_tabs, std::make_pair(M, L), out, [&](BiquadTab** d) {
+    const double fs = c->cfg.sample_rate;
+    const std::vector<BiquadTab> t = {make_biquad_tab(butter2(38.0, fs, true), L),
+                                      make_biquad_tab(butter2(1500.0, fs, true), L)};
+    return upload(c, d, t);
+  });
 }
 int get_kw_tab(omega_ctx* c, int M, BiquadTab** out) { return get_kw_tab(c, M, kw_chunk(M), out); }
 
@@ -751,9 +742,7 @@ int get_any_plan(omega_ctx* c, int N, omega_ctx::AnyPlan** out) {
     if (!e && !pl.radix.empty() && pl.radix.back() > kAnyF32Radix) {
       // a stage of R terms summed in float64 keeps its precision only with unrounded factors: the rounding
       // errors of the float32 table add up over the R terms to the same offset in every output
-      std::vector<double2> tw64(N);
-      for (int m = 0; m < N; ++m) tw64[m] = make_double2(std::cos(2 * kPi * m / N), -std::sin(2 * kPi * m / N));
-      e = upload(c, &pl.tw64, tw64);
+      e = upload(c, &pl.tw64, twiddles64(N, N));
     }
     if (e) return e;
     it = c->any_plans.emplace(N, std::move(pl)).first;

@@ -80,7 +80,9 @@ int omega_harmonic_reset(omega_ctx* c) try {
 
 namespace {
 // np.hamming(m) on the device, cached per audio length: at most kHarmonicWindows tables (a caller that
-// varies m does not grow device memory; past the cap the cache is emptied once the stream is idle)
+// varies m does not grow device memory; past the cap the cache is emptied once the stream is idle). m is any
+// length in 15..8192 and the pointer is fetched per call, so this is the one evicting cache: omega_ctx::tables
+// never frees an entry and must not absorb these.
 constexpr size_t kHarmonicWindows = 8;
 int harmonic_window(omega_ctx* c, int m, double** out) {
   auto it = c->harm.ham.find(m);
@@ -90,10 +92,8 @@ int harmonic_window(omega_ctx* c, int m, double** out) {
       for (auto& kv : c->harm.ham) release(c, kv.second);
       c->harm.ham.clear();
     }
-    std::vector<double> win(m);
-    for (int i = 0; i < m; ++i) win[i] = np_window(OMEGA_WIN_HAMMING, m, i);
     double* d = nullptr;
-    if (int e = upload(c, &d, win)) return e;
+    if (int e = upload(c, &d, np_window64(OMEGA_WIN_HAMMING, m))) return e;
     it = c->harm.ham.emplace(m, d).first;
   }
   *out = it->second;
@@ -386,14 +386,8 @@ int omega_hiphop_features(omega_ctx* c, const float* spectra, int64_t spec_strid
                 kHipHopMinAudio, kHipHopMaxAudio);
   if (n_frames == 0) return 0;
   HIPC(c, hipSetDevice(c->device));
-  auto it = c->hiphop.tw.find(m);
-  if (it == c->hiphop.tw.end()) {
-    std::vector<double2> tw((size_t)m / 2 + 1);
-    for (int q = 0; q <= m / 2; ++q) tw[q] = make_double2(std::cos(2 * M_PI * q / m), -std::sin(2 * M_PI * q / m));
-    double2* d = nullptr;
-    if (int e = upload(c, &d, tw)) return e;
-    it = c->hiphop.tw.emplace(m, d).first;
-  }
+  HipHopParams p = c->hiphop.p;
+  if (int e = get_twiddles64(c, m, m / 2 + 1, &p.tw)) return e;
   const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
   const float* dspec = h.in(spectra, (size_t)((n_frames - 1) * spec_stride + K) * sizeof(float));
@@ -401,12 +395,10 @@ int omega_hiphop_features(omega_ctx* c, const float* spectra, int64_t spec_strid
   double* dout = h.out(out, (size_t)n_frames * kHipHopCols);
   int32_t* dpeaks = h.out(kick_peaks, (size_t)n_frames * kHipHopPeaks);
   if (h.err) return h.err;
-  HipHopParams p = c->hiphop.p;
   p.spec_stride = spec_stride;
   p.f64 = f64 ? 1 : 0;
   p.m = m;
   p.audio_stride = audio_stride;
-  p.tw = it->second;
   // one launch covers at most 2^30 workgroups (two per frame)
   if (int e = for_frame_chunks(n_frames, (int64_t)1 << 29, [&](int64_t f0, int64_t count) -> int {
     HipHopParams q = p;

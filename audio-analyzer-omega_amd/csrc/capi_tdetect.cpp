@@ -29,13 +29,6 @@ bool td_shape_ok(double fs, int K, int m) {
   return std::isfinite(fs) && fs >= kTdMinRate && K >= 2 && K <= kTdMaxBins && is_pow2_in(m, kTdMinFrame, kTdMaxFrame);
 }
 
-int td_hanning(omega_ctx* c, int M, double** out) {
-  if (*out) return 0;
-  std::vector<double> w(M);
-  for (int i = 0; i < M; ++i) w[i] = np_window(OMEGA_WIN_HANN, M, i);
-  return upload(c, out, w);
-}
-
 }  // namespace
 
 extern "C" {
@@ -73,14 +66,10 @@ int omega_tdetect_configure(omega_ctx* c, const omega_tdetect_config* cfg) try {
   TdetectState& v = c->tdetect;
   const double fs = cfg->sample_rate;
   const int K = cfg->n_bins, m = cfg->frame_len;
-  if (!v.sg) {
-    std::vector<double> W(11 * 11);
-    savgol_cubic(11, W.data());
-    if (int e = upload(c, &v.sg, W)) return e;
-  }
-  if (int e = td_hanning(c, kTdFluxLen, &v.han[0])) return e;
-  if (int e = td_hanning(c, kTdNovLen, &v.han[1])) return e;
   TdetectParams p{};
+  if (int e = get_savgol(c, 11, &p.sg)) return e;
+  if (int e = get_window64(c, OMEGA_WIN_HANN, kTdFluxLen, &p.han_f)) return e;
+  if (int e = get_window64(c, OMEGA_WIN_HANN, kTdNovLen, &p.han_n)) return e;
   if (int e = tr_pow2_tables(c, m, &p.tw_m, &p.tw2_m)) return e;
   if (int e = tr_pow2_tables(c, kTdFluxLen, &p.tw_f, &p.tw2_f)) return e;
   if (int e = tr_pow2_tables(c, kTdNovLen, &p.tw_n, &p.tw2_n)) return e;
@@ -90,9 +79,6 @@ int omega_tdetect_configure(omega_ctx* c, const omega_tdetect_config* cfg) try {
   p.nov = m >= kTdNovLen;                     // :324
   p.bin_hz = td_bin_hz(fs, K);
   td_band_indices(fs, K, p.band_idx);
-  p.sg = v.sg;
-  p.han_f = v.han[0];
-  p.han_n = v.han[1];
   if (p.hf) {
     butter4_highpass_ba(5000.0, fs, p.b, p.a);
     lfilter_zi4(p.b, p.a, p.zi);

@@ -6,23 +6,10 @@
 namespace omega_host {
 
 // the float64 tables of hilbert64.hpp's n-point real transform (n a power of two): e^{-2 pi i m / (n / 2)} for
-// m < n / 4 and e^{-2 pi i q / n} for q <= n / 2; kept per n in the transient state
+// m < n / 4 and e^{-2 pi i q / n} for q <= n / 2, each asked for as its period's common table (period / 2 + 1)
 int tr_pow2_tables(omega_ctx* c, int n, const double2** tw, const double2** tw2) {
-  auto it = c->tr.tw.find(n);
-  if (it == c->tr.tw.end()) {
-    const int K = n / 2;
-    std::vector<double2> t1(K / 2 > 0 ? K / 2 : 1), t2(K + 1);
-    for (int m = 0; m < K / 2; ++m) t1[m] = make_double2(std::cos(2 * M_PI * m / K), -std::sin(2 * M_PI * m / K));
-    for (int q = 0; q <= K; ++q) t2[q] = make_double2(std::cos(2 * M_PI * q / n), -std::sin(2 * M_PI * q / n));
-    double2 *d1 = nullptr, *d2 = nullptr;
-    int e = upload(c, &d1, t1);
-    if (!e) e = upload(c, &d2, t2);
-    if (e) return e;
-    it = c->tr.tw.emplace(n, std::make_pair(d1, d2)).first;
-  }
-  *tw = it->second.first;
-  *tw2 = it->second.second;
-  return 0;
+  if (int e = get_twiddles64(c, n / 2, n / 4 + 1, tw)) return e;
+  return get_twiddles64(c, n, n / 2 + 1, tw2);
 }
 
 }  // namespace omega_host
@@ -104,22 +91,15 @@ int omega_transients(omega_ctx* c, const void* x, int32_t f64, int64_t n_frames,
   const bool pow2 = n <= 8192 && !(n & (n - 1));
   if (n_frames == 0) return 0;
   HIPC(c, hipSetDevice(c->device));
-  if (!c->tr.sg) {
-    double W[21][21];
-    savgol_21_3(W);
-    std::vector<double> v(&W[0][0], &W[0][0] + 21 * 21);
-    if (int e = upload(c, &c->tr.sg, v)) return e;
-  }
   TransientParams p{};
+  if (int e = get_savgol(c, 21, &p.sg)) return e;
   if (!pow2) {  // other lengths: the complex mixed-radix transform (transient_any_kernel)
     auto ia = c->tr.any.find(n);
     if (ia == c->tr.any.end()) {
       const std::vector<int> rad = fft_radices(n);
       if ((int)rad.size() > kTrMaxStages) return fail(c, OMEGA_EUNSUP, "transients: length %d: too many factors", n);
-      std::vector<double2> tw(n);
-      for (int m = 0; m < n; ++m) tw[m] = make_double2(std::cos(2 * M_PI * m / n), -std::sin(2 * M_PI * m / n));
       double2* d = nullptr;
-      if (int e = upload(c, &d, tw)) return e;
+      if (int e = upload(c, &d, twiddles64(n, n))) return e;
       ia = c->tr.any.emplace(n, std::make_pair(rad, d)).first;
     }
     p.n_stages = (int)ia->second.first.size();
@@ -134,9 +114,8 @@ int omega_transients(omega_ctx* c, const void* x, int32_t f64, int64_t n_frames,
     if (int e = grow(c, &c->tr.scratch, &c->tr.scratch_cap, per * 2 * (int64_t)n)) return e;
     p.scratch = c->tr.scratch;
   }
-  const double2 *tw = nullptr, *tw2 = nullptr;
   if (pow2)
-    if (int e = tr_pow2_tables(c, n, &tw, &tw2)) return e;
+    if (int e = tr_pow2_tables(c, n, &p.tw, &p.tw2)) return e;
   const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
   const void* dx = h.in(x, (size_t)((n_frames - 1) * frame_stride + n) * el);
@@ -145,14 +124,11 @@ int omega_transients(omega_ctx* c, const void* x, int32_t f64, int64_t n_frames,
   p.f64 = f64 ? 1 : 0;
   p.n = n;
   p.frame_stride = frame_stride;
-  p.sg = c->tr.sg;
   p.fs = c->cfg.sample_rate;
   if (pow2) {
     p.x = dx;
     p.n_frames = n_frames;
     p.out = dout;
-    p.tw = tw;
-    p.tw2 = tw2;
     HIPC(c, launch_transients(p, c->stream));
   } else {
     if (int e = for_frame_chunks(n_frames, per, [&](int64_t f0, int64_t count) -> int {
@@ -244,32 +220,19 @@ int omega_pitch_detect(omega_ctx* c, const void* x, int32_t f64, int64_t n_frame
   }
   if (n != 2048 && n != 4096 && n != 8192)
     return fail(c, OMEGA_EUNSUP, "pitch: frame length %d (2048, 4096 and 8192 are built)", n);
-  auto it = c->pitch.tabs.find(n);
-  if (it == c->pitch.tabs.end()) {
-    std::vector<double2> tw(n + 1);
-    for (int q = 0; q <= n; ++q) tw[q] = make_double2(std::cos(kPi * q / n), -std::sin(kPi * q / n));
-    std::vector<double> win(n);
-    for (int i = 0; i < n; ++i) win[i] = np_window(OMEGA_WIN_HANN, n, i);
-    double2* d1 = nullptr;
-    double* d2 = nullptr;
-    int e = upload(c, &d1, tw);
-    if (!e) e = upload(c, &d2, win);
-    if (e) return e;
-    it = c->pitch.tabs.emplace(n, std::make_pair(d1, d2)).first;
-  }
+  PitchParams p = c->pitch.p;
+  if (int e = get_twiddles64(c, 2 * n, n + 1, &p.tw)) return e;
+  if (int e = get_window64(c, OMEGA_WIN_HANN, n, &p.win)) return e;
   const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
   const void* dx = h.in(x, (size_t)((n_frames - 1) * frame_stride + n) * el);
   double* dout = h.out(out, (size_t)n_frames * kPitchCols);
   if (h.err) return h.err;
-  PitchParams p = c->pitch.p;
   p.x = dx;
   p.f64 = f64 ? 1 : 0;
   p.n_frames = n_frames;
   p.n = n;
   p.frame_stride = frame_stride;
-  p.tw = it->second.first;
-  p.win = it->second.second;
   p.out = dout;
   // one launch covers at most 2^30 workgroups (three per frame)
   if (int e = for_frame_chunks(n_frames, (int64_t)1 << 28, [&](int64_t f0, int64_t count) -> int {
@@ -293,16 +256,11 @@ void omega_phase_config_default(omega_phase_config* cfg) {
   cfg->m = 2048;
 }
 
-namespace {
-// np.hanning(m) by numpy's own route (design.cpp np_window)
-void phase_hanning(int m, double* out) {
-  for (int n = 0; n < m; ++n) out[n] = np_window(OMEGA_WIN_HANN, m, n);
-}
-}  // namespace
-
+// np.hanning(m) by numpy's own route (design.cpp np_window64), as omega_phase_configure uploads it
 int omega_phase_hanning(int32_t m, double* out) try {
   if (!out || m < 2) return OMEGA_EINVAL;
-  phase_hanning(m, out);
+  const std::vector<double> w = np_window64(OMEGA_WIN_HANN, m);
+  std::memcpy(out, w.data(), w.size() * sizeof(double));
   return 0;
 } catch (...) {
   return guard_fail(nullptr);
@@ -341,25 +299,12 @@ int omega_phase_configure(omega_ctx* c, const omega_phase_config* cfg, const dou
   if (omega_phase_band_ranges(cfg->sample_rate, m, edges, ranges))
     return fail(c, OMEGA_EINVAL, "phase: the band edges must be finite");
   HIPC(c, hipSetDevice(c->device));
-  auto it = c->phase.tabs.find(m);
-  if (it == c->phase.tabs.end()) {
-    std::vector<double2> tw((size_t)m / 2);
-    for (int q = 0; q < m / 2; ++q) tw[q] = make_double2(std::cos(2 * M_PI * q / m), -std::sin(2 * M_PI * q / m));
-    std::vector<double> win((size_t)m);
-    phase_hanning(m, win.data());
-    double2* d1 = nullptr;
-    double* d2 = nullptr;
-    int e = upload(c, &d1, tw);
-    if (!e) e = upload(c, &d2, win);
-    if (e) return e;
-    it = c->phase.tabs.emplace(m, std::make_pair(d1, d2)).first;
-  }
   PhaseParams p{};
+  if (int e = get_twiddles64(c, m, m / 2 + 1, &p.tw)) return e;  // (the kernel reads q < m / 2)
+  if (int e = get_window64(c, OMEGA_WIN_HANN, m, &p.hann)) return e;
   p.m = m;
   while ((1 << p.bits) < m) ++p.bits;
   for (int b = 0; b < kPhaseBands; ++b) p.first[b] = ranges[2 * b], p.last[b] = ranges[2 * b + 1];
-  p.tw = it->second.first;
-  p.hann = it->second.second;
   c->phase.p = p;
   c->phase.set = true;
   return 0;

@@ -59,15 +59,8 @@ int omega_voice_configure(omega_ctx* c, const omega_voice_config* cfg) try {
   const int K = cfg->n_bins, m = cfg->frame_len;
   const int w = K > 10 ? std::min(11, K / 4 * 2 + 1) : 0;  // :95-97
   const double* sg = nullptr;
-  if (w) {
-    const int wi = (w - 5) / 2;
-    if (!v.sg[wi]) {
-      std::vector<double> W((size_t)w * w);
-      savgol_cubic(w, W.data());
-      if (int e = upload(c, &v.sg[wi], W)) return e;
-    }
-    sg = v.sg[wi];
-  }
+  if (w)
+    if (int e = get_savgol(c, w, &sg)) return e;
   VoiceParams p{};
   p.n_bins = K;
   p.m = m;

@@ -29,6 +29,18 @@ std::vector<float> make_window(int M, int kind) {
   return w;
 }
 
+std::vector<double> np_window64(int kind, int M) {
+  std::vector<double> w(M);
+  for (int i = 0; i < M; ++i) w[i] = M == 1 ? 1.0 : np_window(kind, M, i);
+  return w;
+}
+
+std::vector<double2> twiddles64(int period, int count) {
+  std::vector<double2> t(count);
+  for (int q = 0; q < count; ++q) t[q] = make_double2(std::cos(2 * M_PI * q / period), -std::sin(2 * M_PI * q / period));
+  return t;
+}
+
 // np.fft.rfftfreq(N, 1/fs)
 double rfreq(int k, int N, double fs) {
   const double d = 1.0 / fs;
@@ -250,52 +262,11 @@ std::vector<int> fft_radices(int n) {
   return rad;
 }
 
-// Savitzky-Golay (21, 3) weights of scipy.signal.savgol_filter's 'interp' mode: the least-squares
-// cubic through the 21 samples of a window evaluated at window position p (p = 10: the interior
-// convolution; p < 10 / p > 10: the first / last 10 outputs of a frame), in centred, scaled
-// coordinates u = (t - 10) / 10 so that the 4 x 4 normal equations stay well conditioned.
-void savgol_21_3(double W[21][21]) {
-  double A[21][4], G[4][4] = {};
-  for (int t = 0; t < 21; ++t)
-    for (int j = 0; j < 4; ++j) A[t][j] = std::pow((t - 10) / 10.0, j);
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j)
-      for (int t = 0; t < 21; ++t) G[i][j] += A[t][i] * A[t][j];
-  double Gi[4][4];  // Gauss-Jordan inverse
-  double M[4][8];
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 8; ++j) M[i][j] = j < 4 ? G[i][j] : (j - 4 == i ? 1.0 : 0.0);
-  for (int c = 0; c < 4; ++c) {
-    int pv = c;
-    for (int r = c + 1; r < 4; ++r)
-      if (std::fabs(M[r][c]) > std::fabs(M[pv][c])) pv = r;
-    for (int j = 0; j < 8; ++j) std::swap(M[c][j], M[pv][j]);
-    const double d = M[c][c];
-    for (int j = 0; j < 8; ++j) M[c][j] /= d;
-    for (int r = 0; r < 4; ++r)
-      if (r != c) {
-        const double f = M[r][c];
-        for (int j = 0; j < 8; ++j) M[r][j] -= f * M[c][j];
-      }
-  }
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) Gi[i][j] = M[i][j + 4];
-  for (int p = 0; p < 21; ++p) {
-    double v[4], q[4] = {};
-    for (int j = 0; j < 4; ++j) v[j] = std::pow((p - 10) / 10.0, j);
-    for (int j = 0; j < 4; ++j)
-      for (int i = 0; i < 4; ++i) q[j] += v[i] * Gi[i][j];
-    for (int t = 0; t < 21; ++t) {
-      double w = 0.0;
-      for (int j = 0; j < 4; ++j) w += q[j] * A[t][j];
-      W[p][t] = w;
-    }
-  }
-}
-
-// savgol_21_3 for any odd window w >= 5: W[p * w + t] is the weight of window sample t in the least-squares
-// cubic's value at window position p (p = w / 2: the interior correlation; the other rows: the 'interp' edges),
-// in the centred, scaled coordinate u = (t - h) / h, h = w / 2.
+// Savitzky-Golay cubic weights of scipy.signal.savgol_filter's 'interp' mode for any odd window w >= 5:
+// W[p * w + t] is the weight of window sample t in the least-squares cubic's value at window position p
+// (p = w / 2: the interior correlation; the other rows: the first / last w / 2 outputs of a frame), in the
+// centred, scaled coordinate u = (t - h) / h, h = w / 2, so that the 4 x 4 normal equations stay well
+// conditioned.
 void savgol_cubic(int w, double* W) {
   const int h = w / 2;
   std::vector<double> A((size_t)w * 4);

@@ -1,5 +1,5 @@
-// Pure host maths of the C API's tables (no HIP call): numpy's windows, np.fft.rfftfreq, scipy's
-// Butterworth designs and their state-space tables, Savitzky-Golay weights, numpy's pairwise-sum leaves.
+// Pure host maths of the C API's tables (no HIP call): numpy's windows, float64 twiddles, np.fft.rfftfreq,
+// scipy's Butterworth designs and their state-space tables, Savitzky-Golay weights, numpy's pairwise-sum leaves.
 // Private to libomega.so: everything here is hidden from the dynamic symbol table.
 #pragma once
 
@@ -17,6 +17,11 @@ inline bool is_pow2_in(int v, int lo, int hi) { return v >= lo && v <= hi && (v 
 // M >= 2 (numpy returns ones(1) for M = 1: make_window's case)
 double np_window(int kind, int M, int i);
 std::vector<float> make_window(int M, int kind);
+// np.blackman / np.hanning / np.hamming (M) whole, in float64: np_window per point, [1.0] for M = 1
+std::vector<double> np_window64(int kind, int M);
+// e^{-2 pi i q / period} for q < count in float64: (cos(2 * M_PI * q / period), -sin(2 * M_PI * q / period)),
+// these operations in this order
+std::vector<double2> twiddles64(int period, int count);
 
 double rfreq(int k, int N, double fs);
 
@@ -38,8 +43,7 @@ omega::BiquadTab make_biquad_tab(const BiquadCoef& c, int L);
 
 // the mixed-radix transforms' stages for length n: 4s, then 2, 3, 5, 7, then the remaining primes
 std::vector<int> fft_radices(int n);
-void savgol_21_3(double W[21][21]);
-// the same for any odd window w >= 5 (cubic): W[p * w + t], p the output's position in the window
+// Savitzky-Golay cubic weights for any odd window w >= 5: W[p * w + t], p the output's position in the window
 void savgol_cubic(int w, double* W);
 void np_leaves(int off, int n, int depth, std::vector<unsigned>& out);
 

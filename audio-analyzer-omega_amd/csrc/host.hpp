@@ -16,6 +16,7 @@
 #include <map>
 #include <new>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/omega.h"
@@ -111,30 +112,26 @@ struct VuState {
   int cur = 0;
 };
 
-// capi_time.cpp -- transient-analysis tables per frame length: twiddles (float64) and the
-// Savitzky-Golay weights
+// capi_time.cpp -- transient analysis: the plans of the lengths that are no power of two up to 8192 (the
+// radices and, beside them, e^{-2 pi i m / n} in float64) and the global work buffer of the longest
 struct TransientState {
-  std::map<int, std::pair<double2*, double2*>> tw;
-  std::map<int, std::pair<std::vector<int>, double2*>> any;  // other lengths: radices, e^{-2 pi i m / n}
+  std::map<int, std::pair<std::vector<int>, double2*>> any;
   double2* scratch = nullptr;
   int64_t scratch_cap = 0;
-  double* sg = nullptr;
 };
 
 // capi_time.cpp -- pitch detection (omega_pitch_configure / omega_pitch_detect): the configuration with
-// its derived periods and high-pass sections, and per frame length the twiddle table and np.hanning window
+// its derived periods and high-pass sections
 struct PitchState {
   bool set = false;
   PitchParams p{};
-  std::map<int, std::pair<double2*, double*>> tabs;
 };
 
 // capi_time.cpp -- stereo phase correlation (omega_phase_configure / omega_phase_correlation): the
-// configuration with the band ranges (no frame state) and per frame length the twiddle table and np.hanning
+// configuration with the band ranges (no frame state)
 struct PhaseState {
   bool set = false;
   PhaseParams p{};
-  std::map<int, std::pair<double2*, double*>> tabs;
 };
 
 // capi_room.cpp -- room acoustics (omega_room_configure / omega_room_modes / omega_room_decay): the
@@ -148,22 +145,19 @@ struct RoomState {
 };
 
 // capi_voice.cpp -- voice detection (omega_voice_configure / omega_voice_features): the configuration with the
-// voice bin range and the lag range (no frame state), and the Savitzky-Golay weights of the four windows
+// voice bin range and the lag range (no frame state)
 struct VoiceState {
   bool set = false;
   VoiceParams p{};
-  double* sg[4] = {};  // windows 5, 7, 9, 11
 };
 
 // capi_tdetect.cpp -- transient detection (omega_tdetect_configure / omega_tdetect_features): the configuration
-// with the band indices and the high-pass design (the stream state travels with the caller), the tables every
-// shape shares, the lfilter carry-scan table per (sample rate, frame length), the per-call workspace and the two
-// state blobs that chain a call's launches
+// with the band indices and the high-pass design (the stream state travels with the caller), the lfilter
+// carry-scan table per (sample rate, frame length), the per-call workspace and the two state blobs that chain a
+// call's launches
 struct TdetectState {
   bool set = false;
   TdetectParams p{};
-  double* sg = nullptr;
-  double* han[2] = {};  // np.hanning(512), np.hanning(1024)
   std::map<std::pair<double, int>, TdScan*> scans;
   double* ws = nullptr;
   int64_t ws_cap = 0;
@@ -171,13 +165,10 @@ struct TdetectState {
 };
 
 // capi_basszoom.cpp -- the bass zoom panel (omega_basszoom_configure / omega_basszoom_features): the configuration
-// with the bar mapping (the panel's state travels with the caller), np.hanning(n) per window length and the
-// 8192-entry twiddle table
+// with the bar mapping (the panel's state travels with the caller)
 struct BassZoomState {
   bool set = false;
   BassZoomParams p{};
-  std::map<int, double*> win;
-  double2* tw = nullptr;
 };
 
 // capi_features.cpp -- the stream state of a feature that compares each frame's spectrum with the one
@@ -201,7 +192,8 @@ struct PrevSpectrum {
 };
 
 // capi_features.cpp -- harmonic analysis (omega_harmonic_configure / omega_harmonic_analyze): the
-// configuration, the stream state and np.hamming per audio length
+// configuration, the stream state and np.hamming per audio length -- a bounded map of its own, emptied when
+// full (harmonic_window), and so kept out of omega_ctx::tables, whose entries are never freed
 struct HarmonicState {
   bool set = false;
   HarmonicParams p{};
@@ -218,13 +210,12 @@ struct GenreState {
 };
 
 // capi_features.cpp -- hip-hop features (omega_hiphop_configure / omega_hiphop_features): the
-// configuration with the band ranges and the three band-pass cascades (no frame state), the designed
-// sections as scipy lays them out, and per frame length the envelope transform's twiddle table
+// configuration with the band ranges and the three band-pass cascades (no frame state) and the designed
+// sections as scipy lays them out
 struct HipHopState {
   bool set = false;
   HipHopParams p{};
   double sos[3][4][6] = {};
-  std::map<int, double2*> tw;
 };
 }  // namespace omega_host
 
@@ -323,6 +314,10 @@ struct omega_ctx {
   std::map<std::pair<int, int>, float*> windows;  // (m, kind) -> device window
   std::map<int, float2*> rots;                     // m -> true-peak rotation table
   std::map<std::pair<int, int>, float4*> wgens;     // (m, kind) -> WinGen table
+  // the feature families' float64 tables (get_twiddles64 / get_window64 / get_savgol below), each under
+  // (its kind, its two parameters). Entries are never evicted: the configured params (phase.p.tw,
+  // tdetect.p.tw_*, basszoom.p.win, voice.p.sg, ...) hold these pointers between calls.
+  std::map<std::tuple<int, int, int>, void*> tables;
   // combine plan as per-target owner lists (CSR) for omega_combine over a subset of resolutions
   int* d_own_off = nullptr;
   int* d_own_rj = nullptr;  // (r << 24) | j
@@ -467,6 +462,38 @@ int cached(M& m, const K& key, typename M::mapped_type* out, B build) {
   }
   *out = it->second;
   return 0;
+}
+
+// A float64 table of omega_ctx::tables: built by build() and uploaded on first use, freed at omega_destroy
+template <class T, class B>
+int host_table(omega_ctx* c, int kind, int a, int b, const T** out, B build) {
+  void* d = nullptr;
+  if (int e = cached(c->tables, std::make_tuple(kind, a, b), &d, [&](void** p) {
+        T* t = nullptr;
+        const int r = upload(c, &t, build());
+        *p = t;
+        return r;
+      }))
+    return e;
+  *out = static_cast<const T*>(d);
+  return 0;
+}
+// e^{-2 pi i q / period}, q < count (design.hpp twiddles64). Keyed by what the caller asks for: families that
+// read a prefix of one period's table ask for the common count, period / 2 + 1, and share one upload.
+inline int get_twiddles64(omega_ctx* c, int period, int count, const double2** out) {
+  return host_table(c, 0, period, count, out, [&] { return twiddles64(period, count); });
+}
+// np.blackman / np.hanning / np.hamming (M) in float64 (design.hpp np_window64; kind: OMEGA_WIN_*)
+inline int get_window64(omega_ctx* c, int kind, int M, const double** out) {
+  return host_table(c, 1, kind, M, out, [&] { return np_window64(kind, M); });
+}
+// the w x w Savitzky-Golay cubic weights (design.hpp savgol_cubic)
+inline int get_savgol(omega_ctx* c, int w, const double** out) {
+  return host_table(c, 2, w, 0, out, [&] {
+    std::vector<double> W((size_t)w * w);
+    savgol_cubic(w, W.data());
+    return W;
+  });
 }
 
 // ---- tables and ordering shared by several families ----
