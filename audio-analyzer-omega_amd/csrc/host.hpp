@@ -59,6 +59,7 @@ hipError_t launch_room_modes(const RoomModesParams& p, hipStream_t s);
 hipError_t launch_room_rt60(const RoomRt60Params& p, hipStream_t s);
 hipError_t launch_voice(const VoiceParams& p, hipStream_t s);
 hipError_t launch_tdetect(const TdetectParams& p, hipStream_t s);
+hipError_t launch_rhythm(const RhythmParams& p, hipStream_t s);
 hipError_t launch_basszoom_frames(const BassZoomParams& p, hipStream_t s);
 hipError_t launch_basszoom_track(const BassZoomParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
@@ -169,6 +170,21 @@ struct TdetectState {
 struct BassZoomState {
   bool set = false;
   BassZoomParams p{};
+};
+
+// capi_rhythm.cpp -- beat detection and band tracking (omega_rhythm_configure / omega_rhythm_features): the
+// configuration with the edges, the uploaded frequency table and the host's copy of it (an unchanged table is not
+// uploaded again), the per-call flag workspace and the two state blobs that chain a call's launches (the stream
+// state travels with the caller)
+struct RhythmState {
+  bool set = false;
+  RhythmParams p{};
+  double* freqs = nullptr;
+  int64_t freqs_cap = 0;
+  std::vector<double> freqs_host;
+  int* ws = nullptr;
+  int64_t ws_cap = 0;
+  double* chain[2] = {};
 };
 
 // capi_features.cpp -- the stream state of a feature that compares each frame's spectrum with the one
@@ -350,6 +366,7 @@ struct omega_ctx {
   VoiceState voice;
   TdetectState tdetect;
   BassZoomState basszoom;
+  RhythmState rhythm;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables

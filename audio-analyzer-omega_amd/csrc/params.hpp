@@ -687,6 +687,37 @@ struct BassZoomParams {
   double *bars, *peaks, *peak_times;  // [n_frames, n_bars] each
 };
 
+// BeatDetector's and FrequencyBandTracker's per-frame sums (rhythm.hip; omega4/panels/beat_detection.py:64-152,
+// :338-349 and frequency_band_tracker.py:71-156): one launch for every frame's flags and sum x^2, then one
+// workgroup per frame for the sums over its spectrum and its predecessor's
+constexpr int kRhCols = 14;          // see include/omega.h for the columns
+constexpr int kRhThreads = 256;
+constexpr int kRhEdges = 10;         // 20, 50, 60, 120, 250, 500, 2000, 4000, 8000, 20000 Hz
+constexpr int kRhBands = 7;
+constexpr int kRhMinBins = 2, kRhMaxBins = 8193;
+constexpr int kRhMaxFrame = 16384;
+constexpr int kRhSums = 3 + kRhBands + 1;  // spec_sum, flux, kick, the bands, spec_fsum
+constexpr double kRhGate = 0.001;    // beat_detection.py:339
+enum RhFlag : int { kRhNonFinite = 1, kRhGated = 2, kRhNoFlux = 4 };
+// the carried state: valid, n_bins, the last live frame's spectrum (float32 values held as float64)
+constexpr int kRhStateHead = 2;
+constexpr int64_t rh_state_len(int n_bins) { return kRhStateHead + (int64_t)n_bins; }
+struct RhythmParams {
+  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values
+  int64_t spec_stride;
+  const void* audio;        // frame f at audio + f * audio_stride, m samples (float32, or float64 when f64); or
+  int64_t audio_stride;     // nullptr: no audio, no gate, sum x^2 is 0
+  int64_t n_frames;
+  int f64;
+  int n_bins, m;
+  const double* freqs;      // [n_bins] the caller's frequency table
+  int edge[kRhEdges];       // the bin of each edge frequency; a band's upper edge 0 reads as n_bins
+  int* ws;                  // [n_frames] each frame's flag bits 0 and 1 (the first launch's; the second's input)
+  const double* state_in;   // [rh_state_len(n_bins)] or nullptr (a stream's first call)
+  double* state_out;        // [rh_state_len(n_bins)] or nullptr
+  double* out;              // [n_frames, kRhCols]
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

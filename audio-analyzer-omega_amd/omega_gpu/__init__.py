@@ -15,10 +15,13 @@ from .room_modes import RoomModeAnalyzer, RoomModeConfig
 from .voice_detection import VoiceDetectionPanel
 from .transient_detection import TransientDetectionPanel
 from .bass_zoom import BassZoomPanel
+from .beat_detection import BeatDetectionPanel, BeatDetector
+from .frequency_band_tracker import FrequencyBandTracker, FrequencyBandTrackerPanel
 
 __all__ = [
     "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector", "PhaseCorrelation",
     "RoomModeAnalyzer", "RoomModeConfig", "VoiceDetectionPanel", "TransientDetectionPanel", "BassZoomPanel",
+    "BeatDetector", "BeatDetectionPanel", "FrequencyBandTracker", "FrequencyBandTrackerPanel",
     "LIB_PATH", "OmegaError", "UnsupportedError", "lib", "Engine", "Resolution", "BandTable",
     "DEFAULT_RESOLUTIONS", "NORTHSTAR_RESOLUTIONS", "METER_KEYS",
     "CepstralAnalyzer", "PitchDetectionConfig", "get_preset_config", "list_presets",

@@ -89,6 +89,10 @@ class BassZoomConfig(C.Structure):
     _fields_ = [("sample_rate", C.c_double), ("frame_len", C.c_int32)]
 
 
+class RhythmConfig(C.Structure):
+    _fields_ = [("n_bins", C.c_int32), ("frame_len", C.c_int32)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -172,6 +176,11 @@ EXPORTS = {
     "omega_basszoom_state_size": (C.c_int64, []),
     "omega_basszoom_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64]
                                 + [C.c_void_p] * 6 + [C.c_int]),
+    "omega_rhythm_config_default": (None, [C.POINTER(RhythmConfig)]),
+    "omega_rhythm_configure": (C.c_int, [C.c_void_p, C.POINTER(RhythmConfig), C.c_void_p, C.c_void_p]),
+    "omega_rhythm_state_size": (C.c_int64, [C.c_int32]),
+    "omega_rhythm_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
+                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -819,6 +819,58 @@ int omega_basszoom_features(omega_ctx* ctx, const void* frames, int64_t frame_st
                             int64_t n_frames, const double* state_in, double* rows, double* bars, double* peaks,
                             double* peak_times, double* state_out, int mem);
 
+/* BeatDetector / BeatDetectionPanel (omega4/panels/beat_detection.py:15-295, :297-384) and FrequencyBandTracker
+ * (omega4/panels/frequency_band_tracker.py:26-240) for consecutive frames of one stream: the sums both panels take
+ * over a frame's spectrum -- the spectral flux against the frame before, the kick band, the seven band energies,
+ * the total, the centroid's numerator and the spread's -- and the beat panel's silence gate. The context keeps
+ * nothing between calls: the caller carries the stream's state, a blob of omega_rhythm_state_size(n_bins) float64
+ * values (a validity flag, n_bins, the last live frame's spectrum as exact float32 values), from state_out of one
+ * call to state_in of the next. state_in NULL: a stream's first frames (a blob recorded for another n_bins counts
+ * as none). state_out NULL: not wanted. Both live where `mem` says and may be the same buffer. One call on F frames
+ * equals F one-frame calls chained through the blob, bit for bit. The entry points are additive to ABI 5.
+ * omega_rhythm_configure fixes the shape and may be repeated; it needs no device until its arguments have passed.
+ * freqs: the caller's frequency table, n_bins float64 values, uploaded when it differs from the configured one.
+ * edges: OMEGA_RHYTHM_EDGES bin indices, np.argmax(freqs >= f) for f = 20, 50, 60, 120, 250, 500, 2000, 4000, 8000,
+ * 20000 Hz, each 0..n_bins (else OMEGA_EINVAL). Where a band's UPPER edge is 0 the band runs to n_bins, the
+ * reference's "beyond spectrum" rule (beat_detection.py:88-89, :146-147, frequency_band_tracker.py:121-122); a
+ * lower edge is taken as it is. Built: n_bins 2..OMEGA_RHYTHM_MAX_BINS, frame_len 1..OMEGA_RHYTHM_MAX_FRAME;
+ * anything else returns OMEGA_EUNSUP and leaves the configured shape as it was.
+ * omega_rhythm_features: frame f has its spectrum (n_bins float32 values s) at spectra + f*spec_stride and, where
+ * frames is not NULL, its frame_len samples x (float32, widened exactly, or float64 when f64) at frames +
+ * f*frame_stride, both in elements; rows may overlap. frames NULL (the tracker's call): no gate, column 1 is 0.
+ * All accumulation is float64. out [n_frames, OMEGA_RHYTHM_COLS] float64:
+ *    0 flags        bit 0: a non-finite sample or bin (every other column is 0, and the frame is passed over: the
+ *                   state goes on as if it had not come); bit 1: gated, sqrt(mean(x^2)) < 0.001 (:338-349) -- the
+ *                   columns are there, but the frame is passed over as a predecessor, as the reference leaves
+ *                   prev_spectrum untouched; bit 2: no live frame before this one in the stream, flux is 0
+ *    1 sumsq        sum x^2
+ *    2 spec_sum     sum s
+ *    3 flux         sum max(0, float32(s - p)), p the predecessor's spectrum: the nearest earlier frame with
+ *                   neither bit 0 nor bit 1, which may be the state's; the difference is rounded to float32 first
+ *    4 kick         sum s[e50:e120]
+ *    5..11 band0..6 sum s[lo:hi] for (20,60), (60,250), (250,500), (500,2000), (2000,4000), (4000,8000),
+ *                   (8000,20000) Hz; 0 where lo >= hi
+ *   12 spec_fsum    sum freqs s
+ *   13 spread_sum   sum (freqs - c)^2 s with c = spec_fsum / (double)(float)spec_sum; 0 where spec_sum <= 0 or c <= 0
+ * state_out: the last live frame of state_in followed by this call's frames; without one, state_in passes through.
+ * Columns 1..12 agree with a float64 evaluation to 1e-12 relative, column 13 to 1e-9. */
+#define OMEGA_RHYTHM_COLS 14
+#define OMEGA_RHYTHM_EDGES 10
+#define OMEGA_RHYTHM_MAX_BINS 8193
+#define OMEGA_RHYTHM_MAX_FRAME 16384
+typedef struct {
+  int32_t n_bins;     /* bins per spectrum (the app: 513) */
+  int32_t frame_len;  /* samples per audio frame (the app: 2048) */
+} omega_rhythm_config;
+/* 513 bins, 2048 samples. */
+void omega_rhythm_config_default(omega_rhythm_config* cfg);
+int omega_rhythm_configure(omega_ctx* ctx, const omega_rhythm_config* cfg, const double* freqs, const int32_t* edges);
+/* 2 + n_bins (0 for n_bins < 1); no context, no device. */
+int64_t omega_rhythm_state_size(int32_t n_bins);
+int omega_rhythm_features(omega_ctx* ctx, const float* spectra, int64_t spec_stride, const void* frames, int32_t f64,
+                          int64_t n_frames, int64_t frame_stride, const double* state_in, double* state_out,
+                          double* out, int mem);
+
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks
  * of chunk_size samples, s16 scaled by 1/32768), its per-chunk noise gate (:620-641: RMS, background
