@@ -38,11 +38,6 @@ constexpr int kT = kBzThreads;
 static_assert(kBzThreads == 4 * 64, "block_sum's default is four waves");
 constexpr int kBzGroup = 8;  // bins a wave holds at once
 
-__device__ __forceinline__ double bz_x(const BassZoomParams& p, int64_t f, int i) {
-  const int64_t k = f * p.frame_stride + i;
-  return p.f64 ? static_cast<const double*>(p.frames)[k] : (double)static_cast<const float*>(p.frames)[k];
-}
-
 // the row's tail from the magnitudes (:168-210), in the reference's operation order and without contraction
 __device__ __forceinline__ void bz_bars(const BassZoomParams& p, const double* mag, double* raw, double* row) {
 #pragma clang fp contract(off)
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(kT) void basszoom_frame_kernel(BassZoomParams p) {
   for (int i = t; i < 64 * A; i += kT) {
     double v = 0.0;
     if (i < p.nw) {
-      v = bz_x(p, f, i);
+      v = p.frames.at(f, i);
       if (!isfinite(v)) bad = 1.0;
       v *= p.win[i];
     }

@@ -114,10 +114,10 @@ int omega_basszoom_features(omega_ctx* c, const void* frames, int64_t frame_stri
       (n_frames > 0 && (!frames || !times || !rows || !bars || !peaks || !peak_times || frame_stride < 1)))
     return fail(c, OMEGA_EINVAL, "basszoom: bad frame layout, or an output or the times missing");
   HIPC(c, hipSetDevice(c->device));
-  const size_t el = f64 ? 8 : 4, sbytes = (size_t)kBzStateLen * sizeof(double), nb = (size_t)cp.n_bars;
+  const size_t sbytes = (size_t)kBzStateLen * sizeof(double), nb = (size_t)cp.n_bars;
   HostCall h(c, mem);
   BassZoomParams p = cp;
-  p.frames = n_frames ? h.in(frames, (size_t)((n_frames - 1) * frame_stride + cp.nw) * el) : nullptr;
+  p.frames = n_frames ? h.rows(frames, frame_stride, cp.nw, f64, n_frames) : Rows{};
   p.times = n_frames ? h.in(times, (size_t)n_frames * sizeof(double)) : nullptr;
   p.state_in = h.in(state_in, sbytes);
   p.rows = n_frames ? h.out(rows, (size_t)n_frames * (kBzRowHead + nb)) : nullptr;
@@ -126,17 +126,10 @@ int omega_basszoom_features(omega_ctx* c, const void* frames, int64_t frame_stri
   p.peak_times = n_frames ? h.out(peak_times, (size_t)n_frames * nb) : nullptr;
   p.state_out = h.out(state_out, (size_t)kBzStateLen);
   if (h.err) return h.err;
-  p.frame_stride = frame_stride;
-  p.f64 = f64 ? 1 : 0;
   p.n_frames = n_frames;
-  if (p.state_out) {
-    // the bars past n_bars: zero in a new panel's blob, else carried (the track kernel writes the first n_bars of
-    // each third; it reads its own entries before it writes them, so one buffer may serve as both blobs)
-    if (!p.state_in)
-      HIPC(c, hipMemsetAsync(p.state_out, 0, sbytes, c->stream));
-    else if (p.state_out != p.state_in)
-      HIPC(c, hipMemcpyAsync(p.state_out, p.state_in, sbytes, hipMemcpyDefault, c->stream));
-  }
+  // the bars past n_bars: zero in a new panel's blob, else carried (the track kernel writes the first n_bars of
+  // each third; it reads its own entries before it writes them, so one buffer may serve as both blobs)
+  if (int e = pass_state_through(c, p.state_in, p.state_out, sbytes)) return e;
   if (n_frames > 0) {
     HIPC(c, launch_basszoom_frames(p, c->stream));
     HIPC(c, launch_basszoom_track(p, c->stream));

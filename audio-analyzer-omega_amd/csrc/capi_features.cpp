@@ -117,27 +117,23 @@ int omega_harmonic_analyze(omega_ctx* c, const float* spectra, int64_t spec_stri
   double* dham = nullptr;
   if (audio)
     if (int e = harmonic_window(c, m, &dham)) return e;
-  const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
-  const float* dspec = h.in(spectra, (size_t)((n_frames - 1) * spec_stride + K) * sizeof(float));
-  const void* daudio = h.in(audio, (size_t)((n_frames - 1) * audio_stride + m) * el);
+  const Rows32 dspec = h.rows32(spectra, spec_stride, K, n_frames);
+  const Rows daudio = h.rows(audio, audio_stride, m, f64, n_frames);
   double* dout = h.out(out, (size_t)n_frames * kHarmonicCols);
   int32_t* dbins = h.out(series_bins, (size_t)n_frames * S * (1 + kHarmonicMaxHarm));
   double* dstr = h.out(series_strength, (size_t)n_frames * S);
   if (h.err) return h.err;
   HarmonicParams p = c->harm.p;
-  p.spec_stride = spec_stride;
-  p.f64 = f64 ? 1 : 0;
   p.m = audio ? m : 0;
-  p.audio_stride = audio_stride;
   p.ham = dham;
   // one launch covers at most 2^30 workgroups (two per frame)
   if (int e = for_frame_chunks(n_frames, (int64_t)1 << 29, [&](int64_t f0, int64_t count) -> int {
     HarmonicParams q = p;
     q.n_frames = count;
-    q.spec = dspec + f0 * spec_stride;
-    q.audio = daudio ? static_cast<const char*>(daudio) + (size_t)(f0 * audio_stride) * el : nullptr;
-    c->harm.stream.chunk(dspec, spec_stride, f0, count, n_frames, &q.prev_in, &q.prev_out);
+    q.spec = dspec.from(f0);
+    q.audio = daudio.from(f0);
+    c->harm.stream.chunk(dspec, f0, count, n_frames, &q.prev_in, &q.prev_out);
     q.out = dout + f0 * kHarmonicCols;
     q.series_bins = dbins ? dbins + f0 * S * (1 + kHarmonicMaxHarm) : nullptr;
     q.series_strength = dstr ? dstr + f0 * S : nullptr;
@@ -167,15 +163,12 @@ int omega_harmonic_metrics(omega_ctx* c, const float* spectrum, const float* pre
   const int K = c->harm.p.n_bins;
   HostCall h(c, mem);
   HarmonicParams p = c->harm.p;  // (the stream state -- the stored previous spectrum -- is neither read nor written)
-  p.spec = h.in(spectrum, (size_t)K * sizeof(float));
-  p.audio = h.in(audio, (size_t)m * (f64 ? 8 : 4));
+  p.spec = h.rows32(spectrum, K, K, 1);
+  p.audio = h.rows(audio, m > 0 ? m : 1, m, f64, 1);
   p.prev_in = h.in(previous, (size_t)K * sizeof(float));
   p.out = h.out(out, (size_t)kHarmonicCols);
   if (h.err) return h.err;
-  p.spec_stride = K;
-  p.f64 = f64 ? 1 : 0;
   p.m = audio ? m : 0;
-  p.audio_stride = m > 0 ? m : 1;
   p.ham = dham;
   p.n_frames = 1;
   p.ungated = 1;
@@ -250,18 +243,14 @@ int omega_genre_features(omega_ctx* c, const float* spectra, int64_t spec_stride
                 kHarmonicMaxAudio);
   if (n_frames == 0) return 0;
   HIPC(c, hipSetDevice(c->device));
-  const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
-  const float* dspec = h.in(spectra, (size_t)((n_frames - 1) * spec_stride + K) * sizeof(float));
-  const void* daudio = h.in(audio, (size_t)((n_frames - 1) * audio_stride + m) * el);
+  const Rows32 dspec = h.rows32(spectra, spec_stride, K, n_frames);
+  const Rows daudio = h.rows(audio, audio_stride, m, f64, n_frames);
   double* dout = h.out(out, (size_t)n_frames * kGenreCols);
   int32_t* dbins = h.out(peak_bins, (size_t)n_frames * kGenrePeaks);
   if (h.err) return h.err;
   GenreParams p = c->genre.p;
-  p.spec_stride = spec_stride;
-  p.f64 = f64 ? 1 : 0;
   p.m = m;
-  p.audio_stride = audio_stride;
   // np.percentile's virtual index (m - 1) q with q = 95 / 100 and 20 / 100 in the audio's precision
   if (f64) {
     const double v95 = (double)(m - 1) * (95.0 / 100.0), v20 = (double)(m - 1) * (20.0 / 100.0);
@@ -278,9 +267,9 @@ int omega_genre_features(omega_ctx* c, const float* spectra, int64_t spec_stride
   if (int e = for_frame_chunks(n_frames, (int64_t)1 << 29, [&](int64_t f0, int64_t count) -> int {
     GenreParams q = p;
     q.n_frames = count;
-    q.spec = dspec + f0 * spec_stride;
-    q.audio = static_cast<const char*>(daudio) + (size_t)(f0 * audio_stride) * el;
-    c->genre.stream.chunk(dspec, spec_stride, f0, count, n_frames, &q.prev_in, &q.prev_out);
+    q.spec = dspec.from(f0);
+    q.audio = daudio.from(f0);
+    c->genre.stream.chunk(dspec, f0, count, n_frames, &q.prev_in, &q.prev_out);
     q.out = dout + f0 * kGenreCols;
     q.peak_bins = dbins + f0 * kGenrePeaks;
     HIPC(c, launch_genre(q, c->stream));
@@ -388,23 +377,19 @@ int omega_hiphop_features(omega_ctx* c, const float* spectra, int64_t spec_strid
   HIPC(c, hipSetDevice(c->device));
   HipHopParams p = c->hiphop.p;
   if (int e = get_twiddles64(c, m, m / 2 + 1, &p.tw)) return e;
-  const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
-  const float* dspec = h.in(spectra, (size_t)((n_frames - 1) * spec_stride + K) * sizeof(float));
-  const void* daudio = h.in(audio, (size_t)((n_frames - 1) * audio_stride + m) * el);
+  const Rows32 dspec = h.rows32(spectra, spec_stride, K, n_frames);
+  const Rows daudio = h.rows(audio, audio_stride, m, f64, n_frames);
   double* dout = h.out(out, (size_t)n_frames * kHipHopCols);
   int32_t* dpeaks = h.out(kick_peaks, (size_t)n_frames * kHipHopPeaks);
   if (h.err) return h.err;
-  p.spec_stride = spec_stride;
-  p.f64 = f64 ? 1 : 0;
   p.m = m;
-  p.audio_stride = audio_stride;
   // one launch covers at most 2^30 workgroups (two per frame)
   if (int e = for_frame_chunks(n_frames, (int64_t)1 << 29, [&](int64_t f0, int64_t count) -> int {
     HipHopParams q = p;
     q.n_frames = count;
-    q.spec = dspec + f0 * spec_stride;
-    q.audio = static_cast<const char*>(daudio) + (size_t)(f0 * audio_stride) * el;
+    q.spec = dspec.from(f0);
+    q.audio = daudio.from(f0);
     q.out = dout + f0 * kHipHopCols;
     q.kick_peaks = dpeaks ? dpeaks + f0 * kHipHopPeaks : nullptr;
     HIPC(c, launch_hiphop(q, c->stream));

@@ -68,50 +68,31 @@ int omega_rhythm_features(omega_ctx* c, const float* spectra, int64_t spec_strid
   if (n_frames < 0 || (n_frames > 0 && (!out || !spectra || spec_stride < 1 || (frames && frame_stride < 1))))
     return fail(c, OMEGA_EINVAL, "rhythm: bad spectrum or audio layout");
   HIPC(c, hipSetDevice(c->device));
-  const size_t el = f64 ? 8 : 4, slen = (size_t)rh_state_len(cp.n_bins), sbytes = slen * sizeof(double);
+  const size_t slen = (size_t)rh_state_len(cp.n_bins);
   HostCall h(c, mem);
-  const float* dspec = n_frames ? h.in(spectra, (size_t)((n_frames - 1) * spec_stride + cp.n_bins) * sizeof(float)) : nullptr;
-  const void* daudio = n_frames && frames ? h.in(frames, (size_t)((n_frames - 1) * frame_stride + cp.m) * el) : nullptr;
-  const double* dsin = h.in(state_in, sbytes);
+  const Rows32 dspec = n_frames ? h.rows32(spectra, spec_stride, cp.n_bins, n_frames) : Rows32{};
+  const Rows daudio = n_frames && frames ? h.rows(frames, frame_stride, cp.m, f64, n_frames) : Rows{};
+  const double* dsin = h.in(state_in, slen * sizeof(double));
   double* dout = n_frames ? h.out(out, (size_t)n_frames * kRhCols) : nullptr;
   double* dsout = h.out(state_out, slen);
   if (h.err) return h.err;
-  if (n_frames == 0) {  // the state passes through
-    if (dsout && dsout != dsin) {
-      if (dsin)
-        HIPC(c, hipMemcpyAsync(dsout, dsin, sbytes, hipMemcpyDefault, c->stream));
-      else
-        HIPC(c, hipMemsetAsync(dsout, 0, sbytes, c->stream));
-    }
+  if (n_frames == 0) {
+    if (int e = pass_state_through(c, dsin, dsout, slen * sizeof(double))) return e;
     return h.finish();
   }
   const int64_t per = std::min(n_frames, kRhChunk);
   if (int e = grow(c, &v.ws, &v.ws_cap, per)) return e;
-  for (double*& b : v.chain)
-    if (!b)
-      if (int e = dalloc(c, &b, (size_t)rh_state_len(kRhMaxBins))) return e;
-  // a call's launches chain through the context's two blobs; the last writes the caller's (through a blob
-  // where the caller's in and out are one buffer: the kernel reads the one while it writes the other)
-  const double* sin = dsin;
-  int k = 0;
-  if (int e = for_frame_chunks(n_frames, per, [&](int64_t f0, int64_t count) -> int {
-        const bool last = f0 + count == n_frames;
-        double* sout = last && dsout != dsin ? dsout : (last && !dsout ? nullptr : v.chain[k]);
+  if (int e = chained_frame_chunks(c, v.chain, (size_t)rh_state_len(kRhMaxBins), slen, n_frames, per, dsin, dsout,
+                                   [&](int64_t f0, int64_t count, const double* sin, double* sout) -> int {
         RhythmParams q = cp;
-        q.f64 = f64 ? 1 : 0;
-        q.spec_stride = spec_stride;
-        q.audio_stride = frame_stride;
         q.n_frames = count;
-        q.spec = dspec + f0 * spec_stride;
-        q.audio = daudio ? static_cast<const char*>(daudio) + (size_t)(f0 * frame_stride) * el : nullptr;
+        q.spec = dspec.from(f0);
+        q.audio = daudio.from(f0);
         q.ws = v.ws;
         q.state_in = sin;
         q.state_out = sout;
         q.out = dout + f0 * kRhCols;
         HIPC(c, launch_rhythm(q, c->stream));
-        if (last && dsout && sout != dsout) HIPC(c, hipMemcpyAsync(dsout, sout, sbytes, hipMemcpyDeviceToDevice, c->stream));
-        sin = sout;
-        k ^= 1;
         return 0;
       }))
     return e;

@@ -85,18 +85,15 @@ int omega_room_modes(omega_ctx* c, const void* spectra, int32_t f64, int64_t spe
   if (n_frames == 0) return 0;
   HIPC(c, hipSetDevice(c->device));
   const int nb = c->room.p.n_bins;
-  const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
-  const void* ds = h.in(spectra, (size_t)((n_frames - 1) * spec_stride + nb) * el);
+  const Rows ds = h.rows(spectra, spec_stride, nb, f64, n_frames);
   double* dout = h.out(out, (size_t)n_frames * kRoomRows * kRoomCols);
   if (h.err) return h.err;
   // one launch covers at most 2^30 workgroups
   if (int e = for_frame_chunks(n_frames, (int64_t)1 << 30, [&](int64_t f0, int64_t count) -> int {
     RoomModesParams q = c->room.p;
-    q.f64 = f64 ? 1 : 0;
-    q.spec_stride = spec_stride;
     q.n_frames = count;
-    q.spec = static_cast<const char*>(ds) + (size_t)(f0 * spec_stride) * el;
+    q.spec = ds.from(f0);
     q.out = dout + f0 * (kRoomRows * kRoomCols);
     HIPC(c, launch_room_modes(q, c->stream));
     return 0;
@@ -116,19 +113,16 @@ int omega_room_decay(omega_ctx* c, const void* audio, int32_t f64, int64_t strea
   if (L > kRt60MaxLen) return fail(c, OMEGA_EUNSUP, "room: %lld samples per history (at most %d)", (long long)L, kRt60MaxLen);
   if (n_streams == 0) return 0;
   HIPC(c, hipSetDevice(c->device));
-  const size_t el = f64 ? 8 : 4;
   const int64_t nf = W > 0 ? L / W : 0;
   HostCall h(c, mem);
-  const void* da = h.in(audio, (size_t)((n_streams - 1) * stream_stride + L) * el);
+  const Rows da = h.rows(audio, stream_stride, L, f64, n_streams);
   double* dout = h.out(out, (size_t)n_streams * kRt60Cols);
   double* den = W > 0 ? h.out(energies, (size_t)(n_streams * nf)) : nullptr;
   if (h.err) return h.err;
   if (int e = for_frame_chunks(n_streams, (int64_t)1 << 30, [&](int64_t s0, int64_t count) -> int {
     RoomRt60Params q{};
-    q.audio = static_cast<const char*>(da) + (size_t)(s0 * stream_stride) * el;
-    q.stream_stride = stream_stride;
+    q.audio = da.from(s0);
     q.n_streams = count;
-    q.f64 = f64 ? 1 : 0;
     q.L = (int)L;
     q.W = (int)W;
     q.fs = c->room.fs;

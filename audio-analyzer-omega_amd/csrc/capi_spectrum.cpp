@@ -293,10 +293,10 @@ int omega_bands_apply(omega_ctx* c, omega_bands* b, const float* spec, int64_t n
   if (n <= 0) return n == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
   HIPC(c, hipSetDevice(c->device));
   HostCall h(c, mem);
-  const float* ds = h.in(spec, ((n - 1) * spec_stride + b->n_bins) * sizeof(float));
+  const Rows32 ds = h.rows32(spec, spec_stride, b->n_bins, n);
   float* dout = h.out(out, (size_t)n * b->n_out);
   if (h.err) return h.err;
-  BandParams p{ds, n, spec_stride, b->n_bins, b->n_out, b->d_starts, b->d_ends, b->d_scale, b->d_bin_scale, b->op,
+  BandParams p{ds.base, n, spec_stride, b->n_bins, b->n_out, b->d_starts, b->d_ends, b->d_scale, b->d_bin_scale, b->op,
                b->n_valid, dout};
   HIPC(c, launch_bands(p, c->stream));
   return h.finish();
@@ -387,7 +387,7 @@ int omega_drum_features(omega_ctx* c, const float* mag, int64_t n_frames, int32_
   }
   if (int e = grow(c, &c->drum.flux, &c->drum.flux_cap, n_frames * kDrumBands)) return e;
   HostCall h(c, mem);
-  const float* dm = h.in(mag, (size_t)((n_frames - 1) * mag_stride + n_bins) * sizeof(float));
+  const Rows32 dm = h.rows32(mag, mag_stride, n_bins, n_frames);
   double* dout = h.out(out, (size_t)n_frames * kDrumCols);
   if (h.err) return h.err;
   // drum_detection.py: bins int(f * len / nyquist) (:86-96, :240-259, :218-219), numpy slices clamp
@@ -396,7 +396,7 @@ int omega_drum_features(omega_ctx* c, const float* mag, int64_t n_frames, int32_
                                        {8000, 15000}};
   const double mult[kDrumBands] = {2.8, 2.8, 2.8, 2.5, 2.3, 2.0, 0.0};  // :78, :295, :300, :305
   DrumParams p{};
-  p.mag = dm;
+  p.mag = dm.base;
   p.n = n_frames;
   p.stride = mag_stride;
   p.n_bins = n_bins;

@@ -8,21 +8,11 @@ namespace {
 
 constexpr int64_t kTdChunk = 65536;  // frames per launch pair (the workspace's rows)
 
-// np.fft.rfftfreq(2 (K - 1), 1 / fs) as numpy evaluates it: val = 1.0 / (n * d), results = arange * val
-double td_bin_hz(double fs, int K) {
-  const double d = 1.0 / fs;
-  return 1.0 / ((double)(2 * (K - 1)) * d);
-}
-
-// np.searchsorted(freqs, [0, 100, 250, 2000, fs / 2]) (side 'left') over the K bins
+// np.searchsorted(freqs, [0, 100, 250, 2000, fs / 2]) over the K bins of np.fft.rfftfreq(2 (K - 1), 1 / fs)
 void td_band_indices(double fs, int K, int* idx) {
-  const double step = td_bin_hz(fs, K);
+  const double step = np_rfftfreq_step(2 * (K - 1), fs);
   const double lim[5] = {0.0, 100.0, 250.0, 2000.0, fs / 2};
-  for (int b = 0; b < 5; ++b) {
-    int k = 0;
-    while (k < K && (double)k * step < lim[b]) ++k;
-    idx[b] = k;
-  }
+  for (int b = 0; b < 5; ++b) idx[b] = searchsorted_left_uniform(step, K, lim[b]);
 }
 
 bool td_shape_ok(double fs, int K, int m) {
@@ -77,7 +67,7 @@ int omega_tdetect_configure(omega_ctx* c, const omega_tdetect_config* cfg) try {
   p.m = m;
   p.hf = m > 256 && 5000.0 / (fs / 2) < 1.0;  // :191, :196
   p.nov = m >= kTdNovLen;                     // :324
-  p.bin_hz = td_bin_hz(fs, K);
+  p.bin_hz = np_rfftfreq_step(2 * (K - 1), fs);
   td_band_indices(fs, K, p.band_idx);
   if (p.hf) {
     butter4_highpass_ba(5000.0, fs, p.b, p.a);
@@ -115,50 +105,31 @@ int omega_tdetect_features(omega_ctx* c, const float* spectra, int64_t spec_stri
   if (n_frames < 0 || (n_frames > 0 && (!out || !spectra || !frames || spec_stride < 1 || frame_stride < 1)))
     return fail(c, OMEGA_EINVAL, "tdetect: bad spectrum or audio layout");
   HIPC(c, hipSetDevice(c->device));
-  const size_t el = f64 ? 8 : 4, sbytes = (size_t)kTdStateLen * sizeof(double);
+  const size_t slen = (size_t)kTdStateLen;
   HostCall h(c, mem);
-  const float* dspec = n_frames ? h.in(spectra, (size_t)((n_frames - 1) * spec_stride + cp.n_bins) * sizeof(float)) : nullptr;
-  const void* daudio = n_frames ? h.in(frames, (size_t)((n_frames - 1) * frame_stride + cp.m) * el) : nullptr;
-  const double* dsin = h.in(state_in, sbytes);
+  const Rows32 dspec = n_frames ? h.rows32(spectra, spec_stride, cp.n_bins, n_frames) : Rows32{};
+  const Rows daudio = n_frames ? h.rows(frames, frame_stride, cp.m, f64, n_frames) : Rows{};
+  const double* dsin = h.in(state_in, slen * sizeof(double));
   double* dout = n_frames ? h.out(out, (size_t)n_frames * kTdCols) : nullptr;
-  double* dsout = h.out(state_out, (size_t)kTdStateLen);
+  double* dsout = h.out(state_out, slen);
   if (h.err) return h.err;
-  if (n_frames == 0) {  // the state passes through
-    if (dsout && dsout != dsin) {
-      if (dsin)
-        HIPC(c, hipMemcpyAsync(dsout, dsin, sbytes, hipMemcpyDefault, c->stream));
-      else
-        HIPC(c, hipMemsetAsync(dsout, 0, sbytes, c->stream));
-    }
+  if (n_frames == 0) {
+    if (int e = pass_state_through(c, dsin, dsout, slen * sizeof(double))) return e;
     return h.finish();
   }
   const int64_t per = std::min(n_frames, kTdChunk);
   if (int e = grow(c, &v.ws, &v.ws_cap, per * kTdWsStride)) return e;
-  for (double*& b : v.chain)
-    if (!b)
-      if (int e = dalloc(c, &b, (size_t)kTdStateLen)) return e;
-  // a call's launches chain through the context's two blobs; the last writes the caller's (through a blob
-  // where the caller's in and out are one buffer: the cross kernel reads the one while it writes the other)
-  const double* sin = dsin;
-  int k = 0;
-  if (int e = for_frame_chunks(n_frames, per, [&](int64_t f0, int64_t count) -> int {
-        const bool last = f0 + count == n_frames;
-        double* sout = last && dsout != dsin ? dsout : (last && !dsout ? nullptr : v.chain[k]);
+  if (int e = chained_frame_chunks(c, v.chain, slen, slen, n_frames, per, dsin, dsout,
+                                   [&](int64_t f0, int64_t count, const double* sin, double* sout) -> int {
         TdetectParams q = cp;
-        q.f64 = f64 ? 1 : 0;
-        q.spec_stride = spec_stride;
-        q.audio_stride = frame_stride;
         q.n_frames = count;
-        q.spec = dspec + f0 * spec_stride;
-        q.audio = static_cast<const char*>(daudio) + (size_t)(f0 * frame_stride) * el;
+        q.spec = dspec.from(f0);
+        q.audio = daudio.from(f0);
         q.ws = v.ws;
         q.state_in = sin;
         q.state_out = sout;
         q.out = dout + f0 * kTdCols;
         HIPC(c, launch_tdetect(q, c->stream));
-        if (last && dsout && sout != dsout) HIPC(c, hipMemcpyAsync(dsout, sout, sbytes, hipMemcpyDeviceToDevice, c->stream));
-        sin = sout;
-        k ^= 1;
         return 0;
       }))
     return e;

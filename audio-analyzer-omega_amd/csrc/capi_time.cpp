@@ -53,18 +53,14 @@ int omega_vu_update(omega_ctx* c, const void* x, int32_t f64, int64_t n_updates,
     if (int e = omega_vu_reset(c)) return e;
   }
   if (int e = grow(c, &c->vu.ms, &c->vu.ms_cap, n_updates * C)) return e;
-  const size_t el = f64 ? 8 : 4;
-  const size_t span = (size_t)((n_updates - 1) * update_stride + (C - 1) * channel_stride + chunk);
   HostCall h(c, mem);
   VuParams p{};
-  p.x = h.in(x, span * el);
+  p.x = h.rows(x, update_stride, (C - 1) * channel_stride + chunk, f64, n_updates);  // (a row: every channel's chunk)
   p.dt = h.in(dt, (size_t)n_updates * sizeof(double));
   p.out = h.out(out, (size_t)n_updates * C * 3);
   if (h.err) return h.err;
-  p.f64 = f64 ? 1 : 0;
   p.n = n_updates;
   p.chunk = chunk;
-  p.frame_stride = update_stride;
   p.channel_stride = channel_stride;
   p.C = C;
   const int a = c->vu.cur, b = a ^ 1;
@@ -116,14 +112,11 @@ int omega_transients(omega_ctx* c, const void* x, int32_t f64, int64_t n_frames,
   }
   if (pow2)
     if (int e = tr_pow2_tables(c, n, &p.tw, &p.tw2)) return e;
-  const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
-  const void* dx = h.in(x, (size_t)((n_frames - 1) * frame_stride + n) * el);
+  const Rows dx = h.rows(x, frame_stride, n, f64, n_frames);
   double* dout = h.out(out, (size_t)n_frames * kTransientCols);
   if (h.err) return h.err;
-  p.f64 = f64 ? 1 : 0;
   p.n = n;
-  p.frame_stride = frame_stride;
   p.fs = c->cfg.sample_rate;
   if (pow2) {
     p.x = dx;
@@ -133,7 +126,7 @@ int omega_transients(omega_ctx* c, const void* x, int32_t f64, int64_t n_frames,
   } else {
     if (int e = for_frame_chunks(n_frames, per, [&](int64_t f0, int64_t count) -> int {
       TransientParams q = p;
-      q.x = static_cast<const char*>(dx) + (size_t)(f0 * frame_stride) * el;
+      q.x = dx.from(f0);
       q.n_frames = count;
       q.out = dout + f0 * kTransientCols;
       HIPC(c, launch_transients_any(q, c->stream));
@@ -223,21 +216,15 @@ int omega_pitch_detect(omega_ctx* c, const void* x, int32_t f64, int64_t n_frame
   PitchParams p = c->pitch.p;
   if (int e = get_twiddles64(c, 2 * n, n + 1, &p.tw)) return e;
   if (int e = get_window64(c, OMEGA_WIN_HANN, n, &p.win)) return e;
-  const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
-  const void* dx = h.in(x, (size_t)((n_frames - 1) * frame_stride + n) * el);
+  const Rows dx = h.rows(x, frame_stride, n, f64, n_frames);
   double* dout = h.out(out, (size_t)n_frames * kPitchCols);
   if (h.err) return h.err;
-  p.x = dx;
-  p.f64 = f64 ? 1 : 0;
-  p.n_frames = n_frames;
   p.n = n;
-  p.frame_stride = frame_stride;
-  p.out = dout;
   // one launch covers at most 2^30 workgroups (three per frame)
   if (int e = for_frame_chunks(n_frames, (int64_t)1 << 28, [&](int64_t f0, int64_t count) -> int {
     PitchParams q = p;
-    q.x = static_cast<const char*>(dx) + (size_t)(f0 * frame_stride) * el;
+    q.x = dx.from(f0);
     q.n_frames = count;
     q.out = dout + f0 * kPitchCols;
     HIPC(c, launch_pitch(q, c->stream));
@@ -320,22 +307,18 @@ int omega_phase_correlation(omega_ctx* c, const void* left, const void* right, i
   if (n_frames == 0) return 0;
   HIPC(c, hipSetDevice(c->device));
   const int m = c->phase.p.m;
-  const size_t el = f64 ? 8 : 4;
-  const size_t span = (size_t)((n_frames - 1) * frame_stride + m) * el;
   HostCall h(c, mem);
-  const void* dl = h.in(left, span);
-  const void* dr = h.in(right, span);
+  const Rows dl = h.rows(left, frame_stride, m, f64, n_frames);
+  const Rows dr = h.rows(right, frame_stride, m, f64, n_frames);
   double* dout = h.out(out, (size_t)n_frames * kPhaseCols);
   double* dpts = h.out(points, (size_t)n_frames * kPhasePoints * 2);
   if (h.err) return h.err;
   // one launch covers at most 2^30 workgroups
   if (int e = for_frame_chunks(n_frames, (int64_t)1 << 30, [&](int64_t f0, int64_t count) -> int {
     PhaseParams q = c->phase.p;
-    q.f64 = f64 ? 1 : 0;
-    q.frame_stride = frame_stride;
     q.n_frames = count;
-    q.left = static_cast<const char*>(dl) + (size_t)(f0 * frame_stride) * el;
-    q.right = static_cast<const char*>(dr) + (size_t)(f0 * frame_stride) * el;
+    q.left = dl.from(f0);
+    q.right = dr.from(f0);
     q.out = dout + f0 * kPhaseCols;
     q.points = dpts ? dpts + f0 * kPhasePoints * 2 : nullptr;
     HIPC(c, launch_phase(q, c->stream));

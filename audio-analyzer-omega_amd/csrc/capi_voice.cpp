@@ -5,19 +5,6 @@
 
 namespace {
 
-// np.fft.rfftfreq(m, 1 / fs) as numpy evaluates it: val = 1.0 / (n * d), results = arange * val
-double rfftfreq_step(double fs, int m) {
-  const double d = 1.0 / fs;
-  return 1.0 / ((double)m * d);
-}
-
-// np.searchsorted(freq_bins, v) (side 'left') over the m / 2 + 1 bins
-int search_bins(double step, int n_freq, double v) {
-  int k = 0;
-  while (k < n_freq && (double)k * step < v) ++k;
-  return k;
-}
-
 bool voice_shape_ok(double fs, int m) {
   return std::isfinite(fs) && fs >= kVoiceMinRate && is_pow2_in(m, kVoiceMinFrame, kVoiceMaxFrame);
 }
@@ -36,9 +23,9 @@ void omega_voice_config_default(omega_voice_config* cfg) {
 
 int omega_voice_bin_range(double sample_rate, int32_t frame_len, int32_t* range) try {
   if (!range || !(sample_rate > 0.0) || !std::isfinite(sample_rate) || frame_len < 1) return OMEGA_EINVAL;
-  const double step = rfftfreq_step(sample_rate, frame_len);
-  range[0] = search_bins(step, frame_len / 2 + 1, 85.0);   // voice_detection.py:63-67
-  range[1] = search_bins(step, frame_len / 2 + 1, 255.0);
+  const double step = np_rfftfreq_step(frame_len, sample_rate);
+  range[0] = searchsorted_left_uniform(step, frame_len / 2 + 1, 85.0);   // voice_detection.py:63-67
+  range[1] = searchsorted_left_uniform(step, frame_len / 2 + 1, 255.0);
   return 0;
 } catch (...) {
   return guard_fail(nullptr);
@@ -65,9 +52,9 @@ int omega_voice_configure(omega_ctx* c, const omega_voice_config* cfg) try {
   p.n_bins = K;
   p.m = m;
   p.n_freq = m / 2 + 1;
-  p.bin_hz = rfftfreq_step(cfg->sample_rate, m);
-  p.voice_start = search_bins(p.bin_hz, p.n_freq, 85.0);
-  p.voice_end = search_bins(p.bin_hz, p.n_freq, 255.0);
+  p.bin_hz = np_rfftfreq_step(m, cfg->sample_rate);
+  p.voice_start = searchsorted_left_uniform(p.bin_hz, p.n_freq, 85.0);
+  p.voice_end = searchsorted_left_uniform(p.bin_hz, p.n_freq, 255.0);
   p.sg_w = w;
   p.sg = sg;
   p.lag_lo = (int)std::min(cfg->sample_rate / 400.0, (double)m);  // :182-183 (Python's int() truncates)
@@ -92,21 +79,17 @@ int omega_voice_features(omega_ctx* c, const float* spectra, int64_t spec_stride
   if (cp.pitch && (!frames || frame_stride < 1)) return fail(c, OMEGA_EINVAL, "voice: bad audio layout");
   if (n_frames == 0) return 0;
   HIPC(c, hipSetDevice(c->device));
-  const size_t el = f64 ? 8 : 4;
   HostCall h(c, mem);
-  const float* dspec = h.in(spectra, (size_t)((n_frames - 1) * spec_stride + cp.n_bins) * sizeof(float));
-  const void* daudio = cp.pitch ? h.in(frames, (size_t)((n_frames - 1) * frame_stride + m) * el) : nullptr;
+  const Rows32 dspec = h.rows32(spectra, spec_stride, cp.n_bins, n_frames);
+  const Rows daudio = cp.pitch ? h.rows(frames, frame_stride, m, f64, n_frames) : Rows{};
   double* dout = h.out(out, (size_t)n_frames * kVoiceCols);
   if (h.err) return h.err;
   // one launch covers at most 2^30 workgroups (two per frame)
   if (int e = for_frame_chunks(n_frames, (int64_t)1 << 29, [&](int64_t f0, int64_t count) -> int {
     VoiceParams q = cp;
-    q.f64 = f64 ? 1 : 0;
-    q.spec_stride = spec_stride;
-    q.audio_stride = frame_stride;
     q.n_frames = count;
-    q.spec = dspec + f0 * spec_stride;
-    q.audio = daudio ? static_cast<const char*>(daudio) + (size_t)(f0 * frame_stride) * el : nullptr;
+    q.spec = dspec.from(f0);
+    q.audio = daudio.from(f0);
     q.out = dout + f0 * kVoiceCols;
     HIPC(c, launch_voice(q, c->stream));
     return 0;

@@ -24,6 +24,18 @@ std::vector<double> np_window64(int kind, int M);
 std::vector<double2> twiddles64(int period, int count);
 
 double rfreq(int k, int N, double fs);
+// np.fft.rfftfreq(n, 1 / fs) as numpy evaluates it: val = 1.0 / (n * d), results = arange * val. Not rfreq: the
+// rounding differs, and the features' golden files pin this one.
+inline double np_rfftfreq_step(int n, double fs) {
+  const double d = 1.0 / fs;
+  return 1.0 / ((double)n * d);
+}
+// np.searchsorted(arange(n_bins) * step, v) (side 'left')
+inline int searchsorted_left_uniform(double step, int n_bins, double v) {
+  int k = 0;
+  while (k < n_bins && (double)k * step < v) ++k;
+  return k;
+}
 
 struct BiquadCoef {
   double b[3], a[3];

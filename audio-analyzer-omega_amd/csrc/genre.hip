@@ -114,7 +114,7 @@ template <class T, class U>
 __device__ __forceinline__ void gn_audio(const GenreParams& p, int64_t f, double* o, unsigned char* smem, double* red,
                                          int* hist, int* sh, int* pick, unsigned* ltab, float* lsum) {
   const int t = threadIdx.x, m = p.m;
-  const T* x = static_cast<const T*>(p.audio) + f * p.audio_stride;
+  const T* x = p.audio.row_as<T>(f);
   U* keys = reinterpret_cast<U*>(smem);
   double bad = 0.0, zc = 0.0, sq = 0.0;
   for (int i = t; i < m; i += kGT) {
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(kGT) void genre_kernel(GenreParams p) {
   double* o = p.out + f * kGenreCols;
 
   if (blockIdx.x & 1) {
-    if (p.f64) gn_audio<double, unsigned long long>(p, f, o, gn_smem, red, hist, sh, pick, ltab, lsum);
+    if (p.audio.f64) gn_audio<double, unsigned long long>(p, f, o, gn_smem, red, hist, sh, pick, ltab, lsum);
     else gn_audio<float, unsigned>(p, f, o, gn_smem, red, hist, sh, pick, ltab, lsum);
     return;
   }
@@ -191,8 +191,8 @@ __global__ __launch_bounds__(kGT) void genre_kernel(GenreParams p) {
   float* mag = reinterpret_cast<float*>(gn_smem);  // [Kp], zero past K
   float* cs = mag + Kp;                             // [Kp] np.cumsum(mag)
   const double* __restrict__ fr = p.freqs;
-  const float* sp = p.spec + f * p.spec_stride;
-  const float* prev = f > 0 ? sp - p.spec_stride : p.prev_in;
+  const float* sp = p.spec.row(f);
+  const float* prev = f > 0 ? p.spec.row(f - 1) : p.prev_in;
   float* keep_out = f == p.n_frames - 1 ? p.prev_out : nullptr;  // stored whatever the frame holds
   int* pb = p.peak_bins + f * kGenrePeaks;
 
@@ -419,7 +419,7 @@ size_t genre_lds_bytes(int n_bins, int m, int f64) {
 
 hipError_t launch_genre(const GenreParams& p, hipStream_t s) {
   if (p.n_frames <= 0) return hipSuccess;
-  const size_t lds = genre_lds_bytes(p.n_bins, p.m, p.f64);
+  const size_t lds = genre_lds_bytes(p.n_bins, p.m, p.audio.f64);
   if (lds + 16 * 1024 > 64 * 1024) {  // (the kernel's static arrays take under 16 KiB)
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&genre_kernel),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -125,8 +125,8 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
     float* str = reinterpret_cast<float*>(pk + kHmMaxPeaks);            // [kHmMaxPeaks] their strength scores
     int* ord = reinterpret_cast<int*>(str + kHmMaxPeaks);               // [kHmMaxPeaks] rank -> index into pk
     const double* __restrict__ fr = p.freqs;
-    const float* sp = p.spec + f * p.spec_stride;
-    const float* prev = f > 0 ? sp - p.spec_stride : p.prev_in;
+    const float* sp = p.spec.row(f);
+    const float* prev = f > 0 ? p.spec.row(f - 1) : p.prev_in;
     float* keep_out = f == p.n_frames - 1 ? p.prev_out : nullptr;  // :264: stored whatever the frame holds
     int* sb = p.series_bins ? p.series_bins + f * p.max_series * (1 + kHarmonicMaxHarm) : nullptr;
     double* ss = p.series_strength ? p.series_strength + f * p.max_series : nullptr;
@@ -402,14 +402,11 @@ __global__ __launch_bounds__(kHT) void harmonic_kernel(HarmonicParams p) {
   // ---- role 1: detect_formants_lpc (:115-196); o[10] = formant count, -1 not converged, -2 non-finite ----
   const int m = p.m;
   double* w = reinterpret_cast<double*>(hm_smem);  // [m]
-  if (!p.audio) {
+  if (!p.audio.base) {
     if (t < 5) o[10 + t] = 0.0;
     return;
   }
-  auto raw = [&](int i) -> double {
-    const int64_t k = f * p.audio_stride + i;
-    return p.f64 ? static_cast<const double*>(p.audio)[k] : (double)static_cast<const float*>(p.audio)[k];
-  };
+  auto raw = [&](int i) { return p.audio.at(f, i); };
   double amax = 0.0, bad = 0.0;
   for (int i = t; i < m; i += kHT) {
     const double x = raw(i);
@@ -541,7 +538,7 @@ size_t harmonic_lds_bytes(int n_bins, int m) {
 
 hipError_t launch_harmonic(const HarmonicParams& p, hipStream_t s) {
   if (p.n_frames <= 0) return hipSuccess;
-  const size_t lds = harmonic_lds_bytes(p.n_bins, p.audio ? p.m : 0);
+  const size_t lds = harmonic_lds_bytes(p.n_bins, p.audio.base ? p.m : 0);
   if (lds + 8 * 1024 > 64 * 1024) {  // (the kernel's static arrays take under 8 KiB)
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&harmonic_kernel),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -66,10 +66,9 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
   double* S = reinterpret_cast<double*>(smem);                          // [m] the filtered signal, the envelope
   double2* Z = reinterpret_cast<double2*>(smem + (size_t)m * 8);        // [m / 2] the transform; then the flags
   double2* sc = reinterpret_cast<double2*>(smem + (size_t)m * 16);      // [kHT]
-  const float* x32 = static_cast<const float*>(p.audio) + f * p.audio_stride;
-  const double* x64 = static_cast<const double*>(p.audio) + f * p.audio_stride;
+  const Row x = p.audio.row(f);
   auto load = [&]() {
-    for (int i = t; i < m; i += kHT) S[i] = p.f64 ? x64[i] : (double)x32[i];
+    for (int i = t; i < m; i += kHT) S[i] = x[i];
     __syncthreads();
   };
   auto filter = [&](int which) {
@@ -104,8 +103,8 @@ __device__ __forceinline__ void hh_audio(const HipHopParams& p, int64_t f, doubl
   }
   sq = block_sum(sq, red);
   double rms;
-  if (!p.f64) {
-    rms = (double)np_rms_f32(x32, m, ltab, lsum, &nl_s);
+  if (!p.audio.f64) {
+    rms = (double)np_rms_f32(p.audio.row_as<float>(f), m, ltab, lsum, &nl_s);
   } else {
     rms = sqrt(sq / (double)m);
   }
@@ -278,7 +277,7 @@ __device__ __forceinline__ void hh_spectrum(const HipHopParams& p, int64_t f, do
   float* mag = reinterpret_cast<float*>(smem);             // [Kp], zero past K
   unsigned char* und = smem + (size_t)Kp * 4;              // [Kp] 1: a peak the distance rule has not decided
   unsigned char* keep = und + Kp;                          // [Kp] 1: a peak the distance rule keeps
-  const float* sp = p.spec + f * p.spec_stride;
+  const float* sp = p.spec.row(f);
   double bad = 0.0;
   for (int i = t; i < Kp; i += kHT) {
     float v = 0.f;

@@ -196,9 +196,8 @@ struct PrevSpectrum {
   int cur = 0;
   bool has_prev = false;
   // prev_in / prev_out of the launch over frames [f0, f0 + count) of a call's n_frames spectra at `spec`
-  void chunk(const float* spec, int64_t stride, int64_t f0, int64_t count, int64_t n_frames, const float** in,
-             float** out) const {
-    *in = f0 ? spec + (f0 - 1) * stride : (has_prev ? prev[cur] : nullptr);
+  void chunk(const Rows32& spec, int64_t f0, int64_t count, int64_t n_frames, const float** in, float** out) const {
+    *in = f0 ? spec.row(f0 - 1) : (has_prev ? prev[cur] : nullptr);
     *out = f0 + count == n_frames ? prev[cur ^ 1] : nullptr;
   }
   void advance() {
@@ -707,6 +706,17 @@ struct HostCall {
     err = stage_out(c, s, p, count, outs, &d);
     return d;
   }
+  // A batch of n_frames rows of `width` elements staged like in(): exactly the span the batch touches
+  Rows rows(const void* p, int64_t stride, int64_t width, int f64, int64_t n_frames) {
+    Rows r{nullptr, stride, f64 ? 1 : 0};
+    r.base = in(p, r.span_bytes(n_frames, width));
+    return r;
+  }
+  Rows32 rows32(const float* p, int64_t stride, int64_t width, int64_t n_frames) {
+    Rows32 r{nullptr, stride};
+    r.base = in(p, r.span_bytes(n_frames, width));
+    return r;
+  }
   int finish() { return host ? finish_host(c, outs) : 0; }
 };
 
@@ -728,6 +738,35 @@ int for_frame_chunks(int64_t n_frames, int64_t per, F body) {
   for (int64_t f0 = 0; f0 < n_frames; f0 += per)
     if (int e = body(f0, std::min(per, n_frames - f0))) return e;
   return 0;
+}
+
+// A call of no frames: the caller's state passes through (a stream's first call: zeros)
+inline int pass_state_through(omega_ctx* c, const double* sin, double* sout, size_t bytes) {
+  if (!sout || sout == sin) return 0;
+  if (sin)
+    HIPC(c, hipMemcpyAsync(sout, sin, bytes, hipMemcpyDefault, c->stream));
+  else
+    HIPC(c, hipMemsetAsync(sout, 0, bytes, c->stream));
+  return 0;
+}
+
+// for_frame_chunks for a family whose launches carry a state of state_len doubles from `sin` to `sout` (either
+// may be null): body(f0, count, state_in, state_out) per launch, chained as frames.hpp's chain_chunks plans
+// through the context's two blobs (allocated here on first use, blob_len doubles each)
+template <class F>
+int chained_frame_chunks(omega_ctx* c, double* (&blob)[2], size_t blob_len, size_t state_len, int64_t n_frames,
+                         int64_t per, const double* sin, double* sout, F body) {
+  for (double*& b : blob)
+    if (!b)
+      if (int e = dalloc(c, &b, blob_len)) return e;
+  auto at = [&](ChainBuf b) { return b == kChainOut ? sout : (b == kChainNone ? nullptr : blob[b]); };
+  auto launch = [&](int64_t f0, int64_t count, ChainBuf read, ChainStep s) -> int {
+    double* w = at(s.write);
+    if (int e = body(f0, count, read == kChainIn ? sin : at(read), w)) return e;
+    if (s.copy_back) HIPC(c, hipMemcpyAsync(sout, w, state_len * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  };
+  return chain_chunks(n_frames, per, sout != nullptr, sout == sin, launch);
 }
 
 }  // namespace omega_host

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "frames.hpp"
+
 namespace omega {
 
 constexpr int kMaxRes = 4;
@@ -354,13 +356,12 @@ struct RfftParams {
 };
 
 // VU meter ballistics (vu.hip; vu_meters.py:55-99) over n consecutive update calls of chunk samples
-// per channel: update u of channel c at x + u * frame_stride + c * channel_stride (float32 or float64)
+// per channel: update u is row u of x, channel c at c * channel_stride in it
 struct VuParams {
-  const void* x;
-  int f64;
+  Rows x;
   int64_t n;
   int chunk;
-  int64_t frame_stride, channel_stride;
+  int64_t channel_stride;
   int C;
   const double* dt;        // [n] seconds since the previous update
   const double* hist_in;   // [C, Wv] the last hist_n samples before this batch, oldest first
@@ -377,11 +378,9 @@ struct VuParams {
 constexpr int kTransientCols = 6;  // detected, attack_time_ms, punch, envelope_peak, envelope_rms, envelope_mean
 constexpr int kTrMaxStages = 32;
 struct TransientParams {
-  const void* x;
-  int f64;
+  Rows x;                   // the frames, n samples each
   int64_t n_frames;
   int n;                    // frame length (>= 64; powers of two up to 8192 on the packed transform)
-  int64_t frame_stride;
   const double2* tw;        // [n/4] e^{-2 pi i m / (n/2)}
   const double2* tw2;       // [n/2 + 1] e^{-2 pi i q / n}
   const double* sg;         // [21, 21] Savitzky-Golay (21, 3) weights by output position in the window
@@ -423,11 +422,9 @@ struct Weight64Params {
 constexpr int kPitchCols = 10;  // pitch, confidence, cepstral / autocorrelation / YIN (pitch, confidence), rms, flags
 constexpr int kPitchThreads = 256;
 struct PitchParams {
-  const void* x;            // frame f at x + f * frame_stride (float32, or float64 when f64)
-  int f64;
+  Rows x;                   // the frames, n samples each
   int64_t n_frames;
   int n;                    // 2048, 4096 or 8192
-  int64_t frame_stride;
   double fs, min_pitch, max_pitch;
   int min_period, max_period;
   double yin_threshold;
@@ -451,14 +448,11 @@ constexpr int kHarmonicMinBins = 16, kHarmonicMaxBins = 8193;
 constexpr int kHarmonicMinAudio = 15, kHarmonicMaxAudio = 8192;
 constexpr int kHarmonicLpcOrder = 14;
 struct HarmonicParams {
-  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 magnitudes
-  int64_t spec_stride;
+  Rows32 spec;              // n_bins float32 magnitudes per frame
   int n_bins;
   const double* freqs;      // [n_bins] strictly increasing
-  const void* audio;        // frame f at audio + f * audio_stride (float32, or float64 when f64); nullptr: none
-  int f64;
+  Rows audio;               // m samples per frame; a null base: none
   int m;                    // audio samples per frame
-  int64_t audio_stride;
   const double* ham;        // [m] np.hamming(m)
   int64_t n_frames;
   double fs, nyquist;
@@ -484,14 +478,11 @@ constexpr int kGenrePeaks = 5;   // compute_harmonic_distortion weighs the five 
 // mid [500, 2000], upper (2000, 8000], and the flatness range [100, 4000]
 constexpr int kGenreBands = 10;
 struct GenreParams {
-  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values (|.| is taken)
-  int64_t spec_stride;
+  Rows32 spec;              // n_bins float32 values per frame (|.| is taken)
   int n_bins;
   const double* freqs;      // [n_bins] strictly increasing
-  const void* audio;        // frame f at audio + f * audio_stride (float32, or float64 when f64)
-  int f64;
+  Rows audio;               // m samples per frame
   int m;                    // audio samples per frame
-  int64_t audio_stride;
   int64_t n_frames;
   int band_lo[kGenreBands], band_n[kGenreBands];  // first bin and bin count of each range (0: no bins)
   int rank95, rank20;       // floor(q (m - 1)) for np.percentile's q = 0.95 and 0.20, in the audio's precision
@@ -514,13 +505,10 @@ constexpr int kHipHopMinAudio = 64, kHipHopMaxAudio = 8192;
 // vocal [300, 2000], and every bin
 constexpr int kHipHopBands = 9;
 struct HipHopParams {
-  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values (|.| is taken)
-  int64_t spec_stride;
+  Rows32 spec;              // n_bins float32 values per frame (|.| is taken)
   int n_bins;
-  const void* audio;        // frame f at audio + f * audio_stride, m samples (float32, or float64 when f64)
-  int f64;
+  Rows audio;               // m samples per frame
   int m;
-  int64_t audio_stride;
   int64_t n_frames;
   int band_lo[kHipHopBands], band_n[kHipHopBands];  // first bin and bin count of each range (0: no bins)
   W64Stage sos[3][4];       // sub-bass, kick, hi-hat: four DF2T sections each (b0, b1, b2, a1, a2)
@@ -538,11 +526,8 @@ constexpr int kPhasePoints = 128;  // ceil(m / max(1, m / 100)) is 128 at m = 12
 constexpr int kPhaseThreads = 256;
 constexpr int kPhaseMinFrame = 64, kPhaseMaxFrame = 8192;
 struct PhaseParams {
-  const void* left;         // frame f at left + f * frame_stride and right + f * frame_stride, m samples each
-  const void* right;
-  int64_t frame_stride;
+  Rows left, right;         // m samples per frame each, of one stride and one precision
   int64_t n_frames;
-  int f64;                  // the samples are float64 (else float32, widened on load)
   int m, bits;              // m = 1 << bits
   int first[kPhaseBands], last[kPhaseBands];  // the masks' bin ranges [first, last) (equal: no bins)
   const double* hann;       // [m] np.hanning(m)
@@ -562,10 +547,8 @@ constexpr int kRoomThreads = 256;
 constexpr int kRt60Threads = 1024, kRt60Cols = 8;
 constexpr int kRt60MaxLen = 1 << 20;
 struct RoomModesParams {
-  const void* spec;         // frame f at spec + f * spec_stride, n_bins values
-  int64_t spec_stride;
+  Rows spec;                // n_bins values per frame
   int64_t n_frames;
-  int f64;                  // the spectra are float64 (else float32, widened on load)
   int n_bins;
   int first, last;          // the in-range bins [first, last) of the caller's table
   int freqs_bad;            // the table holds a non-finite entry: every frame gets flag bit 0
@@ -575,10 +558,8 @@ struct RoomModesParams {
   double* out;              // [n_frames, kRoomRows, kRoomCols]
 };
 struct RoomRt60Params {
-  const void* audio;        // stream s at audio + s * stream_stride, L samples
-  int64_t stream_stride;
+  Rows audio;               // one row of L samples per stream
   int64_t n_streams;
-  int f64;
   int L, W;                 // W > 0: frames of W samples (W divides L), their sums of squares to `energies`
   double fs;
   double* out;              // [n_streams, kRt60Cols]
@@ -597,12 +578,9 @@ constexpr double kVoiceMinRate = 8000.0;
 constexpr int kVoiceLagBlock = 4;    // lags per thread of the autocorrelation
 constexpr int kVoicePad = 8;         // zeros behind the staged audio frame (the lag block's overrun)
 struct VoiceParams {
-  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values
-  int64_t spec_stride;
-  const void* audio;        // frame f at audio + f * audio_stride, m samples (float32, or float64 when f64)
-  int64_t audio_stride;
+  Rows32 spec;              // n_bins float32 values per frame
+  Rows audio;               // m samples per frame
   int64_t n_frames;
-  int f64;
   int n_bins, m;
   int n_freq;               // m / 2 + 1: len(np.fft.rfftfreq(m, 1 / fs))
   double bin_hz;            // rfftfreq's factor 1.0 / (m * (1 / fs)): freq_bins[k] = k * bin_hz
@@ -637,12 +615,9 @@ struct TdScan {
   double Pl[64][16];        // P^(lane + 1)
 };
 struct TdetectParams {
-  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values
-  int64_t spec_stride;
-  const void* audio;        // frame f at audio + f * audio_stride, m samples (float32, or float64 when f64)
-  int64_t audio_stride;
+  Rows32 spec;              // n_bins float32 values per frame
+  Rows audio;               // m samples per frame
   int64_t n_frames;
-  int f64;
   int n_bins, m;
   int n_roles;
   int roles[kTdRoles];      // the roles launched, in grid order (workgroup b: roles[b / n_frames], frame b % n_frames)
@@ -671,10 +646,8 @@ constexpr int kBzMaxBars = 64, kBzMaxBins = 256;  // include/omega.h states both
 constexpr int kBzRowHead = 3;        // flags, bass_max, scale_factor, then n_bars compressed values
 constexpr int kBzStateLen = 3 * kBzMaxBars;       // bars, peaks, peak timestamps (each kBzMaxBars float64)
 struct BassZoomParams {
-  const void* frames;       // frame f at frames + f * frame_stride (float32, or float64 when f64)
-  int64_t frame_stride;
+  Rows frames;              // nw samples read per frame
   int64_t n_frames;
-  int f64;
   int nw;                   // samples read per frame: min(frame_len, kBzFft)
   int first_bin, n_valid, bins_per_bar, n_bars;
   double comp[kBzMaxBars];  // 0.3 / 0.6 / 1.0 / 0.8 by the bar's centre frequency
@@ -703,12 +676,9 @@ enum RhFlag : int { kRhNonFinite = 1, kRhGated = 2, kRhNoFlux = 4 };
 constexpr int kRhStateHead = 2;
 constexpr int64_t rh_state_len(int n_bins) { return kRhStateHead + (int64_t)n_bins; }
 struct RhythmParams {
-  const float* spec;        // frame f at spec + f * spec_stride, n_bins float32 values
-  int64_t spec_stride;
-  const void* audio;        // frame f at audio + f * audio_stride, m samples (float32, or float64 when f64); or
-  int64_t audio_stride;     // nullptr: no audio, no gate, sum x^2 is 0
+  Rows32 spec;              // n_bins float32 values per frame
+  Rows audio;               // m samples per frame; a null base: no audio, no gate, sum x^2 is 0
   int64_t n_frames;
-  int f64;
   int n_bins, m;
   const double* freqs;      // [n_bins] the caller's frequency table
   int edge[kRhEdges];       // the bin of each edge frequency; a band's upper edge 0 reads as n_bins

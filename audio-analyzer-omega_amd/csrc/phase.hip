@@ -63,10 +63,7 @@ __global__ __launch_bounds__(kPT) void phase_kernel(PhaseParams p) {
   const int64_t f = blockIdx.x;
   double2* Z = reinterpret_cast<double2*>(ph_smem);  // [m + 16], slot(i) = i + (i >> sk)
   auto slot = [sk](int i) { return i + (i >> sk); };
-  const float* l32 = static_cast<const float*>(p.left) + f * p.frame_stride;
-  const float* r32 = static_cast<const float*>(p.right) + f * p.frame_stride;
-  const double* l64 = static_cast<const double*>(p.left) + f * p.frame_stride;
-  const double* r64 = static_cast<const double*>(p.right) + f * p.frame_stride;
+  const Row xl = p.left.row(f), xr = p.right.row(f);
   double* o = p.out + f * kPhaseCols;
   double* pts = p.points ? p.points + f * (kPhasePoints * 2) : nullptr;
   if (t == 0) {
@@ -77,7 +74,7 @@ __global__ __launch_bounds__(kPT) void phase_kernel(PhaseParams p) {
   // the frame, the means (:153-154)
   double a[3] = {0.0, 0.0, 0.0};
   for (int i = t; i < m; i += kPT) {
-    const double l = p.f64 ? l64[i] : (double)l32[i], r = p.f64 ? r64[i] : (double)r32[i];
+    const double l = xl[i], r = xr[i];
     Z[slot(i)] = make_double2(l, r);
     if (!isfinite(l) || !isfinite(r)) a[0] = 1.0;
     a[1] += l;
@@ -110,7 +107,7 @@ __global__ __launch_bounds__(kPT) void phase_kernel(PhaseParams p) {
     const int step = max(1, m / 100), i = t * step;
     double x = 0.0, y = 0.0;
     if (i < m) {
-      const double l = p.f64 ? l64[i] : (double)l32[i], r = p.f64 ? r64[i] : (double)r32[i];
+      const double l = xl[i], r = xr[i];
       const double mid = (l + r) / 2.0, side = (l - r) / 2.0, rt2 = 1.4142135623730951;  // math.sqrt(2)
       x = (mid - side) / rt2 * 0.5;
       y = (mid + side) / rt2 * 0.5;

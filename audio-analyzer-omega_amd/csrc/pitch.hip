@@ -98,10 +98,7 @@ __global__ __launch_bounds__(kPT) void pitch_kernel(PitchParams p) {
   double2* sc = reinterpret_cast<double2*>(pt_smem + (size_t)n * 16);     // [kPT]
   double* red = reinterpret_cast<double*>(sc + kPT);                       // [4]
   double* o = p.out + f * kPitchCols;
-  auto raw = [&](int i) -> double {
-    const int64_t k = f * p.frame_stride + i;
-    return p.f64 ? static_cast<const double*>(p.x)[k] : (double)static_cast<const float*>(p.x)[k];
-  };
+  auto raw = [&](int i) { return p.x.at(f, i); };
   auto xin = [&](int i) -> float { return (float)raw(i); };  // the reference's astype(np.float32) (:587-588)
   int bits = 0;
   while ((1 << bits) < n) ++bits;  // log2 n

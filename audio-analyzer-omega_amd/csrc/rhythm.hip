@@ -31,11 +31,6 @@ namespace {
 
 constexpr int kT = kRhThreads;
 
-__device__ __forceinline__ double rh_x(const RhythmParams& p, int64_t f, int i) {
-  const int64_t k = f * p.audio_stride + i;
-  return p.f64 ? static_cast<const double*>(p.audio)[k] : (double)static_cast<const float*>(p.audio)[k];
-}
-
 // The nearest live frame before `before` (uniform; -1: none in this launch), 256 frames per step
 __device__ __forceinline__ int64_t rh_predecessor(const RhythmParams& p, int64_t before, double* red) {
   for (int64_t base = before - 1; base >= 0; base -= kT) {
@@ -54,19 +49,19 @@ __global__ __launch_bounds__(kT) void rhythm_flags_kernel(RhythmParams p) {
   const int t = threadIdx.x;
   const int64_t f = blockIdx.x;
   double v[2] = {0.0, 0.0};  // non-finite count, sum x^2
-  if (p.audio)
+  if (p.audio.base)
     for (int i = t; i < p.m; i += kT) {
-      const double x = rh_x(p, f, i);
+      const double x = p.audio.at(f, i);
       if (!isfinite(x)) v[0] = 1.0;
       v[1] = fma(x, x, v[1]);
     }
-  const float* g = p.spec + f * p.spec_stride;
+  const float* g = p.spec.row(f);
   for (int i = t; i < p.n_bins; i += kT)
     if (!isfinite(g[i])) v[0] = 1.0;
   block_sums<2, kT / 64>(v, red);
   if (t == 0) {
     const bool bad = v[0] > 0.0;
-    const bool gated = !bad && p.audio && sqrt(v[1] / (double)p.m) < kRhGate;
+    const bool gated = !bad && p.audio.base && sqrt(v[1] / (double)p.m) < kRhGate;
     p.ws[f] = bad ? kRhNonFinite : (gated ? kRhGated : 0);
     p.out[f * kRhCols + 1] = bad ? 0.0 : v[1];
   }
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(kT) void rhythm_kernel(RhythmParams p) {
     if (!so) return;
     const int64_t last = rh_predecessor(p, F, red);
     if (last >= 0) {
-      const float* g = p.spec + last * p.spec_stride;
+      const float* g = p.spec.row(last);
       for (int i = t; i < K; i += kT) so[kRhStateHead + i] = (double)g[i];
     } else {
       for (int i = t; i < K; i += kT) so[kRhStateHead + i] = has_state ? sin[kRhStateHead + i] : 0.0;
@@ -104,9 +99,9 @@ __global__ __launch_bounds__(kT) void rhythm_kernel(RhythmParams p) {
     return;
   }
   const int64_t prev = rh_predecessor(p, f, red);
-  const float* pg = prev >= 0 ? p.spec + prev * p.spec_stride : nullptr;
+  const float* pg = prev >= 0 ? p.spec.row(prev) : nullptr;
   const bool has_prev = pg || has_state;
-  const float* g = p.spec + f * p.spec_stride;
+  const float* g = p.spec.row(f);
   // a band's upper edge 0 is the reference's "beyond the spectrum": the band runs to the last bin
   auto upper = [&](int e) { return p.edge[e] == 0 ? K : p.edge[e]; };
   const int kick_lo = p.edge[1], kick_hi = upper(3);

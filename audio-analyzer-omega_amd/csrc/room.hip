@@ -70,8 +70,7 @@ __global__ __launch_bounds__(kRT) void room_modes_kernel(RoomModesParams p) {
   double* mq = msev + P;
   double* mprom = mq + P;
   int* pk = reinterpret_cast<int*>(mprom + P);     // [P] per peak: its in-range bin
-  const float* s32 = static_cast<const float*>(p.spec) + f * p.spec_stride;
-  const double* s64 = static_cast<const double*>(p.spec) + f * p.spec_stride;
+  const Row sp = p.spec.row(f);
   const double* fr = p.freqs + p.first;
   double* o = p.out + f * (kRoomRows * kRoomCols);
   if (t == 0) npk = 0;
@@ -79,7 +78,7 @@ __global__ __launch_bounds__(kRT) void room_modes_kernel(RoomModesParams p) {
   // :52 over the whole spectrum; the in-range bins and their sum
   double a[2] = {0.0, 0.0};
   for (int i = t; i < p.n_bins; i += kRT) {
-    const double v = p.f64 ? s64[i] : (double)s32[i];
+    const double v = sp[i];
     if (!isfinite(v)) a[0] = 1.0;
     if (i >= p.first && i < p.last) {
       x[i - p.first] = v;
@@ -191,11 +190,10 @@ namespace {
 // the samples of [lo, hi) from the back, with curve[i] = behind + (running sum of squares inside the chunk);
 // stops below `stop`
 template <class F>
-__device__ __forceinline__ void rt_sweep(const RoomRt60Params& p, const float* a32, const double* a64, int lo, int hi,
-                                         int stop, double behind, F body) {
+__device__ __forceinline__ void rt_sweep(Row a, int lo, int hi, int stop, double behind, F body) {
   double run = 0.0;
   for (int i = hi - 1; i >= lo && i >= stop; --i) {
-    const double v = p.f64 ? a64[i] : (double)a32[i];
+    const double v = a[i];
     run += v * v;
     body(i, behind + run);
   }
@@ -209,8 +207,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
   __shared__ double wtot[NW];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, L = p.L;
   const int64_t s = blockIdx.x;
-  const float* a32 = static_cast<const float*>(p.audio) + s * p.stream_stride;
-  const double* a64 = static_cast<const double*>(p.audio) + s * p.stream_stride;
+  const Row a = p.audio.row(s);
   double* o = p.out + s * kRt60Cols;
   const int chunk = (L + kTT - 1) / kTT, lo = min(t * chunk, L), hi = min(lo + chunk, L);
 
@@ -221,7 +218,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
       double e = 0.0;
       for (int i = lane; i < p.W; i += 64) {
         const int64_t at = (int64_t)k * p.W + i;
-        const double v = p.f64 ? a64[at] : (double)a32[at];
+        const double v = a[at];
         e += v * v;
       }
 #pragma unroll
@@ -232,7 +229,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
 
   // the chunk sums and their suffix scan
   double cs = 0.0, nf1[1] = {0.0};
-  rt_sweep(p, a32, a64, lo, hi, 0, 0.0, [&](int, double cv) { cs = cv; });
+  rt_sweep(a, lo, hi, 0, 0.0, [&](int, double cv) { cs = cv; });
   if (!isfinite(cs)) nf1[0] = 1.0;  // (a non-finite sample or square makes its chunk's sum non-finite)
   double inc = cs;  // sum over the lanes >= this one of the wave
 #pragma unroll
@@ -256,7 +253,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
 
   // :371-382, :436 the crossings as counts
   double cnt[3] = {0.0, 0.0, 0.0};
-  rt_sweep(p, a32, a64, lo, hi, 0, behind, [&](int, double cv) {
+  rt_sweep(a, lo, hi, 0, behind, [&](int, double cv) {
     const double db = 10.0 * log10(fmax(cv, 1e-10) / den);
     cnt[0] += db > -5.0 ? 1.0 : 0.0;
     cnt[1] += db > -10.0 ? 1.0 : 0.0;
@@ -280,7 +277,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
   // :388-406 the line of db on t = i / fs over [i5, i35), centred
   const int b1 = min(hi, i35);  // (the sweeps stop below i5 and skip i >= i35 in their bodies)
   double mu[2] = {0.0, 0.0};
-  rt_sweep(p, a32, a64, lo, hi, i5, behind, [&](int i, double cv) {
+  rt_sweep(a, lo, hi, i5, behind, [&](int i, double cv) {
     if (i >= b1) return;
     mu[0] += (double)i / p.fs;
     mu[1] += 10.0 * log10(fmax(cv, 1e-10) / den);
@@ -288,7 +285,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
   block_sums<2, NW>(mu, red);
   const double mt = mu[0] / (double)n, md = mu[1] / (double)n;
   double cen[3] = {0.0, 0.0, 0.0};
-  rt_sweep(p, a32, a64, lo, hi, i5, behind, [&](int i, double cv) {
+  rt_sweep(a, lo, hi, i5, behind, [&](int i, double cv) {
     if (i >= b1) return;
     const double dt = (double)i / p.fs - mt, dd = 10.0 * log10(fmax(cv, 1e-10) / den) - md;
     cen[0] += dt * dt;
@@ -298,7 +295,7 @@ __global__ __launch_bounds__(kTT) void room_rt60_kernel(RoomRt60Params p) {
   block_sums<3, NW>(cen, red);
   const double slope = cen[1] / cen[0], icpt = md - slope * mt;
   double ssr[1] = {0.0};
-  rt_sweep(p, a32, a64, lo, hi, i5, behind, [&](int i, double cv) {
+  rt_sweep(a, lo, hi, i5, behind, [&](int i, double cv) {
     if (i >= b1) return;
     const double r = 10.0 * log10(fmax(cv, 1e-10) / den) - (slope * ((double)i / p.fs) + icpt);
     ssr[0] += r * r;

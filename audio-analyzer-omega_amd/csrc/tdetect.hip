@@ -42,17 +42,12 @@ constexpr int kT = kTdThreads;
 static_assert(kTdThreads == kTrThreads, "hilbert64.hpp's loops stride by kTrThreads");
 constexpr double kTdPi = 3.14159265358979323846;
 
-__device__ __forceinline__ double td_x(const TdetectParams& p, int64_t f, int i) {
-  const int64_t k = f * p.audio_stride + i;
-  return p.f64 ? static_cast<const double*>(p.audio)[k] : (double)static_cast<const float*>(p.audio)[k];
-}
-
 // > 0 where frame f holds a non-finite sample or bin (every thread gets the answer)
 __device__ __forceinline__ bool td_bad(const TdetectParams& p, int64_t f, double* red) {
   double bad = 0.0;
   for (int i = threadIdx.x; i < p.m; i += kT)
-    if (!isfinite(td_x(p, f, i))) bad = 1.0;
-  const float* g = p.spec + f * p.spec_stride;
+    if (!isfinite(p.audio.at(f, i))) bad = 1.0;
+  const float* g = p.spec.row(f);
   for (int i = threadIdx.x; i < p.n_bins; i += kT)
     if (!isfinite(g[i])) bad = 1.0;
   return block_sum(bad, red) > 0.0;
@@ -65,7 +60,7 @@ __device__ __forceinline__ void td_envelope(const TdetectParams& p, int64_t f, d
     if (threadIdx.x == 0) o[1] = 0.0;
     return;
   }
-  auto xin = [&](int i) { return td_x(p, f, i); };
+  auto xin = [&](int i) { return p.audio.at(f, i); };
   double2* spare = nullptr;
   const double* env = tr_hilbert_env(xin, m, smem, smem + m / 2, p.tw_m, p.tw2_m, &spare);
   double s = 0.0;
@@ -96,7 +91,7 @@ __device__ __forceinline__ void td_flux(const TdetectParams& p, int64_t f, doubl
   double2* B = smem + K;
   for (int k = t; k < K; k += kT) {
     const int i0 = 2 * k, i1 = 2 * k + 1;
-    A[k] = make_double2(i0 < p.m ? td_x(p, f, i0) * p.han_f[i0] : 0.0, i1 < p.m ? td_x(p, f, i1) * p.han_f[i1] : 0.0);
+    A[k] = make_double2(i0 < p.m ? p.audio.at(f, i0) * p.han_f[i0] : 0.0, i1 < p.m ? p.audio.at(f, i1) * p.han_f[i1] : 0.0);
   }
   __syncthreads();
   const double2* Z = tr_fft(A, B, K, p.tw_f);
@@ -131,8 +126,8 @@ __device__ __forceinline__ void td_novelty(const TdetectParams& p, int64_t f, do
   const int base = p.m - kTdNovLen;  // (>= 0: the role runs from m = 1024 on)
   auto pe = [&](int i) {
     const int j = base + i;
-    const double v = td_x(p, f, j);
-    return (j == 0 ? v : v - 0.97 * td_x(p, f, j - 1)) * p.han_n[i];
+    const double v = p.audio.at(f, j);
+    return (j == 0 ? v : v - 0.97 * p.audio.at(f, j - 1)) * p.han_n[i];
   };
   double2* A = smem;
   double2* B = smem + K;
@@ -223,15 +218,15 @@ __device__ __forceinline__ void td_hf(const TdetectParams& p, int64_t f, double2
     if (t == 0) o[8] = 0.0;
     return;
   }
-  const double x0 = td_x(p, f, 0), xl = td_x(p, f, m - 1);
+  const double x0 = p.audio.at(f, 0), xl = p.audio.at(f, m - 1);
   for (int j = t; j < n; j += kT) {
     double v;
     if (j >= E && j < E + m)
-      v = td_x(p, f, j - E);
+      v = p.audio.at(f, j - E);
     else if (j < E)
-      v = 2.0 * x0 - td_x(p, f, E - j);  // odd_ext
+      v = 2.0 * x0 - p.audio.at(f, E - j);  // odd_ext
     else
-      v = 2.0 * xl - td_x(p, f, m - 2 - (j - E - m));
+      v = 2.0 * xl - p.audio.at(f, m - 2 - (j - E - m));
     ext[j] = v;
   }
   __syncthreads();
@@ -250,7 +245,7 @@ __device__ __forceinline__ void td_scalar(const TdetectParams& p, int64_t f, dou
   const int t = threadIdx.x, m = p.m, K = p.n_bins;
   double* o = p.out + f * kTdCols;
   double* x = reinterpret_cast<double*>(smem);  // [m]
-  const float* g = p.spec + f * p.spec_stride;
+  const float* g = p.spec.row(f);
   if (t == 0) {
     ii[0] = m;      // the first argmax
     ii[1] = 0;      // start: the last i < peak below a tenth of the peak
@@ -259,7 +254,7 @@ __device__ __forceinline__ void td_scalar(const TdetectParams& p, int64_t f, dou
   }
   double bad = 0.0;
   for (int i = t; i < m; i += kT) {
-    const double v = td_x(p, f, i);
+    const double v = p.audio.at(f, i);
     if (!isfinite(v)) bad = 1.0;
     x[i] = v;
   }

@@ -110,10 +110,7 @@ __global__ __launch_bounds__(kTrThreads) void transient_kernel(TransientParams p
   double2* A = tr_smem;
   double2* B = tr_smem + K;
   const int64_t f = blockIdx.x;
-  auto xin = [&](int i) -> double {
-    const int64_t k = f * p.frame_stride + i;
-    return p.f64 ? static_cast<const double*>(p.x)[k] : (double)static_cast<const float*>(p.x)[k];
-  };
+  auto xin = [&](int i) { return p.x.at(f, i); };
   // 1-3) the envelope |hilbert(x)| (hilbert64.hpp)
   double2* Hz = nullptr;
   double* env = tr_hilbert_env(xin, N, A, B, p.tw, p.tw2, &Hz);
@@ -157,10 +154,7 @@ __global__ __launch_bounds__(kTrThreads) void transient_any_kernel(TransientPara
   const int64_t f = blockIdx.x;
   double2* A = p.scratch ? p.scratch + f * 2 * (int64_t)N : tr_any_smem;
   double2* B = A + N;
-  auto xin = [&](int i) -> double {
-    const int64_t k = f * p.frame_stride + i;
-    return p.f64 ? static_cast<const double*>(p.x)[k] : (double)static_cast<const float*>(p.x)[k];
-  };
+  auto xin = [&](int i) { return p.x.at(f, i); };
   for (int i = threadIdx.x; i < N; i += kTrThreads) A[i] = make_double2(xin(i), 0.0);
   __syncthreads();
   double2* X = tr_fft_any(A, B, p);

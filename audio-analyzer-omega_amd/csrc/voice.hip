@@ -41,13 +41,10 @@ constexpr int kVT = kVoiceThreads, kVW = kVoiceThreads / 64;
 
 // 1.0 where frame f's audio holds a non-finite sample (this thread's share)
 __device__ __forceinline__ double vc_audio_bad(const VoiceParams& p, int64_t f) {
-  const float* a32 = static_cast<const float*>(p.audio) + f * p.audio_stride;
-  const double* a64 = static_cast<const double*>(p.audio) + f * p.audio_stride;
+  const Row a = p.audio.row(f);
   double bad = 0.0;
-  for (int i = threadIdx.x; i < p.m; i += kVT) {
-    const double v = p.f64 ? a64[i] : (double)a32[i];
-    if (!isfinite(v)) bad = 1.0;
-  }
+  for (int i = threadIdx.x; i < p.m; i += kVT)
+    if (!isfinite(a[i])) bad = 1.0;
   return bad;
 }
 
@@ -56,7 +53,7 @@ __device__ __forceinline__ void voice_spectrum(const VoiceParams& p, int64_t f, 
   const int t = threadIdx.x, K = p.n_bins;
   float* s = reinterpret_cast<float*>(smem);  // [K] the spectrum
   float* sm = s + K;                          // [K] savgol_filter's result
-  const float* g = p.spec + f * p.spec_stride;
+  const float* g = p.spec.row(f);
   double* o = p.out + f * kVoiceCols;
   const int vs = p.voice_start, ve = p.voice_end;
   if (t < 4) first[t] = K;
@@ -145,20 +142,19 @@ __device__ __forceinline__ void voice_audio(const VoiceParams& p, int64_t f, uns
   constexpr int B = kVoiceLagBlock;
   const int t = threadIdx.x, m = p.m;
   double* x = reinterpret_cast<double*>(smem);  // [m + kVoicePad]
-  const float* a32 = static_cast<const float*>(p.audio) + f * p.audio_stride;
-  const double* a64 = static_cast<const double*>(p.audio) + f * p.audio_stride;
+  const Row au = p.audio.row(f);
   double* o = p.out + f * kVoiceCols;
 
   double a[2] = {0.0, 0.0};  // non-finite, c[0]
   for (int i = t; i < m + kVoicePad; i += kVT) {
     double v = 0.0;
-    if (i < m) v = p.f64 ? a64[i] : (double)a32[i];
+    if (i < m) v = au[i];
     if (!isfinite(v)) a[0] = 1.0;
     x[i] = v;
     a[1] = fma(v, v, a[1]);
   }
   {
-    const float* g = p.spec + f * p.spec_stride;
+    const float* g = p.spec.row(f);
     for (int i = t; i < p.n_bins; i += kVT)
       if (!isfinite(g[i])) a[0] = 1.0;
   }

@@ -22,8 +22,7 @@ __device__ __forceinline__ double vu_sample(const VuParams& p, int64_t pos, int 
   // pos: position in history ++ batch; the history holds hist_n samples, oldest first
   if (pos < p.hist_n) return p.hist_in[c * p.Wv + pos];
   const int64_t q = pos - p.hist_n, u = q / p.chunk, i = q % p.chunk;
-  const int64_t k = u * p.frame_stride + c * p.channel_stride + i;
-  return p.f64 ? static_cast<const double*>(p.x)[k] : (double)static_cast<const float*>(p.x)[k];
+  return p.x.at(u, c * p.channel_stride + i);
 }
 
 __global__ __launch_bounds__(256) void vu_ms_kernel(VuParams p) {

@@ -304,6 +304,38 @@ def test_chaining_is_bit_equal(G, det, g):
 
 
 @pytest.mark.gpu
+def test_multi_launch_chain_is_bit_equal(det):
+    """A call of more than 65536 frames takes several launches that hand the state on through the context's two
+    blobs. 65537 frames of K = 2 bins without audio, the smallest such call: non-finite rows lie on both sides of
+    the launch boundary (65535, 65536) and before it, so the last launch finds its predecessor, and the call its
+    outgoing state, in the launch before. One call equals the chained calls 65536 + 1 and 1 + 65536, and the same
+    call through the C entry point with state_in and state_out in one buffer, bit for bit."""
+    from omega_gpu import _lib as L
+    F, K = 65537, 2
+    spec = np.random.default_rng(11).random((F, K), dtype=np.float32)
+    bad = {3: np.nan, 40000: np.inf, 65534: -np.inf, 65535: np.nan, 65536: np.inf}
+    for i, v in bad.items():
+        spec[i, i & 1] = v
+    freqs = np.array([0.0, 100.0])
+    rows, state = det.analyze_frames(spec, None, freqs)
+    flags = rows[:, 0].astype(int) & RR.FLAG_NONFINITE
+    assert sorted(np.flatnonzero(flags)) == sorted(bad)
+    np.testing.assert_array_equal(state, np.concatenate([[1.0, K], spec[65533].astype(np.float64)]))
+    for cut in (65536, 1):
+        a, sa = det.analyze_frames(spec[:cut], None, freqs)
+        b, sb = det.analyze_frames(spec[cut:], None, freqs, sa)
+        np.testing.assert_array_equal(np.concatenate([a, b]), rows)
+        np.testing.assert_array_equal(sb, state)
+    buf = np.zeros(len(state))  # (a blob that is not valid: a stream's first call)
+    out = np.empty_like(rows)
+    det._dev._eng._check(L.lib().omega_rhythm_features(
+        det._dev._eng._ctx, spec.ctypes.data, K, None, 0, F, 0, buf.ctypes.data, buf.ctypes.data, out.ctypes.data,
+        L.MEM_HOST))
+    np.testing.assert_array_equal(out, rows)
+    np.testing.assert_array_equal(buf, state)
+
+
+@pytest.mark.gpu
 def test_all_gated_call_passes_the_state_through(G, det):
     spec, frames, freqs = inputs(G, "app")
     _, state = det.analyze_frames(spec, frames, freqs)

@@ -111,13 +111,13 @@ def main():
     ap.add_argument("--bins", type=int, default=512, help="genre: spectrum bins per frame (512, 4097)")
     ap.add_argument("--lib", default=None, help="another build in lib/ (A/B of two builds on one box)")
     a = ap.parse_args()
+    if a.lib:
+        from omega_gpu import _lib as L0
+        L0.use_development_library(a.lib)
     if a.stage == "room":
         return room(a.reps)
     if a.stage == "voice":
         return voice(a.reps)
-    if a.lib:
-        from omega_gpu import _lib as L0
-        L0.use_development_library(a.lib)
     import bench
     from omega_gpu import NORTHSTAR_RESOLUTIONS, Engine
     from omega_gpu import _lib as L
