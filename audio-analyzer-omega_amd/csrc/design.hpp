@@ -1,4 +1,4 @@
-// Pure host maths of the C API's tables (no HIP call): numpy's windows, float64 twiddles, np.fft.rfftfreq,
+// Pure host maths of the C API's tables (no HIP call): numpy's windows, float64 twiddles, np.fft.rfftfreq, np.linspace,
 // scipy's Butterworth designs and their state-space tables, Savitzky-Golay weights, numpy's pairwise-sum leaves.
 // Private to libomega.so: everything here is hidden from the dynamic symbol table.
 #pragma once
@@ -35,6 +35,18 @@ inline int searchsorted_left_uniform(double step, int n_bins, double v) {
   int k = 0;
   while (k < n_bins && (double)k * step < v) ++k;
   return k;
+}
+
+// np.linspace(0, stop, num)[k] as numpy evaluates it (num >= 2, stop != 0): step = stop / (num - 1), arange * step,
+// and the last point is stop itself
+inline double np_linspace0(int k, int num, double stop) {
+  return k == num - 1 ? stop : (double)k * (stop / (double)(num - 1));
+}
+// np.argmax(np.linspace(0, stop, num) >= v): the first such index, 0 where there is none
+inline int linspace0_argmax_ge(int num, double stop, double v) {
+  for (int k = 0; k < num; ++k)
+    if (np_linspace0(k, num, stop) >= v) return k;
+  return 0;
 }
 
 struct BiquadCoef {

@@ -62,6 +62,8 @@ hipError_t launch_tdetect(const TdetectParams& p, hipStream_t s);
 hipError_t launch_rhythm(const RhythmParams& p, hipStream_t s);
 hipError_t launch_basszoom_frames(const BassZoomParams& p, hipStream_t s);
 hipError_t launch_basszoom_track(const BassZoomParams& p, hipStream_t s);
+hipError_t launch_waterfall(const WaterfallParams& p, hipStream_t s);
+hipError_t launch_waterfall_colors(const WaterfallColorParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -184,6 +186,14 @@ struct RhythmState {
   std::vector<double> freqs_host;
   int* ws = nullptr;
   int64_t ws_cap = 0;
+  double* chain[2] = {};
+};
+
+// capi_waterfall.cpp -- the spectrogram waterfall (omega_waterfall_configure / omega_waterfall_rows): the configured
+// shape and the two state blobs that chain a call's launches (the panel's state travels with the caller)
+struct WaterfallState {
+  bool set = false;
+  int n_bins = 0, first_bin = 0, n_cells = 0;
   double* chain[2] = {};
 };
 
@@ -366,6 +376,7 @@ struct omega_ctx {
   TdetectState tdetect;
   BassZoomState basszoom;
   RhythmState rhythm;
+  WaterfallState waterfall;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables

@@ -688,6 +688,39 @@ struct RhythmParams {
   double* out;              // [n_frames, kRhCols]
 };
 
+// SpectrogramWaterfall's per-frame update and colour map (waterfall.hip; omega4/panels/spectrogram_waterfall.py
+// :71-121, :142-205, :295-305): one launch for every frame's flags, argmax, dB maximum and minimum, then one
+// workgroup per frame for the sliding percentiles, the normalised row and its colours
+constexpr int kWfThreads = 256;
+constexpr int kWfMaxBins = 8193;     // include/omega.h states the cap
+constexpr int kWfCols = 7;           // flags, dB max, dB min, peak, floor, argmax index, argmax value
+constexpr int kWfHist = 20;          // the (max, min) pairs the percentiles see (:95-96)
+enum WfFlag : int { kWfNonFinite = 1 };
+// the carried state: valid, dtype tag (1: float64), count, kWfHist maxima and kWfHist minima oldest first (float32
+// values widened exactly), the current peak and floor
+constexpr int kWfStateMax = 3, kWfStateMin = kWfStateMax + kWfHist, kWfStatePeak = kWfStateMin + kWfHist;
+constexpr int kWfStateLen = kWfStatePeak + 2;
+struct WaterfallParams {
+  Rows spec;                // n_bins values per frame
+  int64_t n_frames;
+  int n_bins, first_bin, n_cells;
+  int auto_gain;            // 0: the carried peak and floor stay in force (:93)
+  double gain_db;           // gain_adjustment (:111), rounded to the input's type
+  int scheme;               // 0 spectrum, 1 hot, 2 cool, 3 viridis, any other grey (:147-203)
+  const double* state_in;   // [kWfStateLen] or nullptr (a new panel: peak 0, floor -80)
+  double* state_out;        // [kWfStateLen] or nullptr
+  double* stats;            // [n_frames, kWfCols]
+  void* rows;               // [n_frames, n_cells] in the input's type
+  unsigned char* rgb;       // [n_frames, n_cells, 3] or nullptr
+};
+// the stand-alone colour map: intensities [n_rows, n_cells] -> rgb [n_rows, n_cells, 3]
+struct WaterfallColorParams {
+  Rows in;
+  int64_t n_rows;
+  int n_cells, scheme;
+  unsigned char* rgb;
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

@@ -17,8 +17,10 @@ from .transient_detection import TransientDetectionPanel
 from .bass_zoom import BassZoomPanel
 from .beat_detection import BeatDetectionPanel, BeatDetector
 from .frequency_band_tracker import FrequencyBandTracker, FrequencyBandTrackerPanel
+from .spectrogram_waterfall import SpectrogramWaterfall, SpectrogramWaterfallPanel
 
 __all__ = [
+    "SpectrogramWaterfall", "SpectrogramWaterfallPanel",
     "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector", "PhaseCorrelation",
     "RoomModeAnalyzer", "RoomModeConfig", "VoiceDetectionPanel", "TransientDetectionPanel", "BassZoomPanel",
     "BeatDetector", "BeatDetectionPanel", "FrequencyBandTracker", "FrequencyBandTrackerPanel",

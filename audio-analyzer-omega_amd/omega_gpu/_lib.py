@@ -93,6 +93,10 @@ class RhythmConfig(C.Structure):
     _fields_ = [("n_bins", C.c_int32), ("frame_len", C.c_int32)]
 
 
+class WaterfallConfig(C.Structure):
+    _fields_ = [("n_bins", C.c_int32), ("first_bin", C.c_int32), ("n_cells", C.c_int32)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -181,6 +185,14 @@ EXPORTS = {
     "omega_rhythm_state_size": (C.c_int64, [C.c_int32]),
     "omega_rhythm_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "omega_waterfall_config_default": (None, [C.POINTER(WaterfallConfig)]),
+    "omega_waterfall_mapping": (C.c_int, [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "omega_waterfall_configure": (C.c_int, [C.c_void_p, C.POINTER(WaterfallConfig)]),
+    "omega_waterfall_state_size": (C.c_int64, []),
+    "omega_waterfall_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_double,
+                                       C.c_int32] + [C.c_void_p] * 5 + [C.c_int]),
+    "omega_waterfall_colors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -43,6 +43,9 @@
  *                          :600-783 (§8(f) row 7)
  *   omega_basszoom_*       BassZoomPanel.setup_bass_mapping            omega4/panels/bass_zoom.py:51-97 and
  *                          _process_bass_detail_internal               bass_zoom.py:141-232 (§8(f) row 12)
+ *   omega_waterfall_*      SpectrogramWaterfall.update, _spectrum_to_color omega4/panels/spectrogram_waterfall.py:56-121,
+ *                          :142-205 and SpectrogramWaterfallPanel.update  :295-305 (omega_waterfall_config_default,
+ *                          _mapping, _configure, _state_size, _rows, _colors)
  *
  * Conventions:
  *   - every function returns 0 on success and a negative omega_status on error; the message is
@@ -870,6 +873,68 @@ int64_t omega_rhythm_state_size(int32_t n_bins);
 int omega_rhythm_features(omega_ctx* ctx, const float* spectra, int64_t spec_stride, const void* frames, int32_t f64,
                           int64_t n_frames, int64_t frame_stride, const double* state_in, double* state_out,
                           double* out, int mem);
+
+/* SpectrogramWaterfall / SpectrogramWaterfallPanel (omega4/panels/spectrogram_waterfall.py:56-121, :142-205,
+ * :295-305) for consecutive frames of one stream: the dB row of the displayed slice, its auto-range over the last 20
+ * frames, the normalised row and its colours. All arithmetic runs in the input's precision as numpy 2.x runs the
+ * reference: float32 spectra give float32 rows, peak and floor, float64 spectra float64. The context keeps nothing
+ * between calls: the caller carries the panel's state, a blob of omega_waterfall_state_size() float64 values that do
+ * not depend on the slice (a validity flag, a dtype tag -- 1 for float64 --, a count, 20 dB maxima and 20 dB minima
+ * oldest first with float32 values widened exactly, the current peak and floor), from state_out of one call to
+ * state_in of the next; it survives a change of the slice as the reference's peak_history survives
+ * set_frequency_range. state_in NULL: a new panel (peak 0, floor -80). state_out NULL: not wanted. Both live where
+ * `mem` says and may be the same buffer. A blob recorded in the other precision returns OMEGA_EUNSUP: a stream has
+ * one precision (for OMEGA_MEM_DEVICE the call reads the blob's head back, which waits for the context's stream).
+ * One call on F frames equals F one-frame calls chained through the blob, bit for bit; n_frames 0 passes the state
+ * through. The entry points are additive to ABI 5.
+ * omega_waterfall_mapping: _setup_frequency_mapping (:56-69) -- freq_bins = np.linspace(0, sample_rate / 2,
+ * fft_size / 2 + 1) as numpy evaluates it, first_bin = argmax(freq_bins >= min_freq), end_bin = argmax(freq_bins >=
+ * max_freq) with 0 read as the last index; the row is bins [first_bin, end_bin). No context, no device.
+ * omega_waterfall_configure fixes the shape and may be repeated; it needs no device. Built: n_bins
+ * 1..OMEGA_WATERFALL_MAX_BINS, n_cells >= 1, first_bin >= 0, first_bin + n_cells <= n_bins; anything else returns
+ * OMEGA_EUNSUP and leaves the configured shape as it was.
+ * omega_waterfall_rows: frame f has its n_bins values x (float32, or float64 when f64) at spectra + f*spec_stride
+ * elements; rows may overlap. Per frame: dB = 20 log10(max(x, 1e-10)) over the slice (log10 evaluated in float64
+ * of the exactly widened value; for float32 input rounded to float32, then multiplied by 20 in float32), (max dB,
+ * min dB) join the history, with auto_gain the peak is np.percentile(last 20 maxima, 95) and the floor
+ * np.percentile(last 20 minima, 5) (method 'linear', numpy's _lerp, in the input's precision), without it the
+ * carried peak and floor stay; row = clip((dB + gain_db - floor) / (peak - floor), 0, 1), zeros where peak - floor
+ * is not positive.
+ *   stats [n_frames, OMEGA_WATERFALL_COLS] float64:
+ *     0 flags   bit 0: a non-finite bin anywhere in the frame (every other column and the row are 0, rgb holds the
+ *               zero row's colours, and the frame is passed over: the state goes on as if it had not come)
+ *     1 db_max, 2 db_min   of the slice
+ *     3 peak, 4 floor      current_peak / current_floor after this frame
+ *     5 argmax index, 6 argmax value   np.argmax over all n_bins (first occurrence) and the bin there (:302-305)
+ *   rows [n_frames, n_cells] in the input's type
+ *   rgb  uint8 [n_frames, n_cells, 3], or NULL (scheme is then ignored): omega_waterfall_colors of the rows
+ * float64 rows agree with numpy's to 1e-12 absolute (the library's log10 against the C library's); float32 rows to
+ * 8 * 2^-24 absolute (numpy's float32 log10 is not correctly rounded).
+ * omega_waterfall_colors: _spectrum_to_color (:142-205) of intensities [n_rows, n_cells] (row r at intensity +
+ * r*row_stride elements) -> rgb uint8 [n_rows, n_cells, 3]; needs no configuration. scheme: 0 spectrum, 1 hot,
+ * 2 cool, 3 viridis (through colorsys.hsv_to_rgb), any other value the reference's grey fallback. Each component
+ * is int(255 * ...), a truncation, of IEEE add / subtract / multiply / divide in the intensity's precision with the
+ * literals rounded to it first, without contraction: bit for bit the reference's bytes. */
+#define OMEGA_WATERFALL_COLS 7
+#define OMEGA_WATERFALL_MAX_BINS 8193
+#define OMEGA_WATERFALL_HISTORY 20
+typedef struct {
+  int32_t n_bins;     /* bins per spectrum (the app: 1025) */
+  int32_t first_bin;  /* the slice's first bin (the app: 1) */
+  int32_t n_cells;    /* bins in the slice (the app: 853) */
+} omega_waterfall_config;
+/* 1025 bins, cells [1, 854). */
+void omega_waterfall_config_default(omega_waterfall_config* cfg);
+int omega_waterfall_mapping(double sample_rate, int32_t fft_size, double min_freq, double max_freq, int32_t* first_bin,
+                            int32_t* end_bin);
+int omega_waterfall_configure(omega_ctx* ctx, const omega_waterfall_config* cfg);
+/* 45; no context, no device. */
+int64_t omega_waterfall_state_size(void);
+int omega_waterfall_rows(omega_ctx* ctx, const void* spectra, int64_t spec_stride, int32_t f64, int64_t n_frames,
+                         int32_t auto_gain, double gain_db, int32_t scheme, const double* state_in, double* state_out,
+                         double* stats, void* rows, uint8_t* rgb, int mem);
+int omega_waterfall_colors(omega_ctx* ctx, const void* intensity, int64_t row_stride, int32_t f64, int64_t n_rows,
+                           int32_t n_cells, int32_t scheme, uint8_t* rgb, int mem);
 
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Run one stage of the cfg2 hot path in isolation (for rocprofv3 counter passes and A/B timing).
 
-  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre,room,voice} [--reps N]
+  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre,room,voice,waterfall} [--reps N]
 
 spectra-bands / spectra-chroma / spectra-mag: the cfg3 kernel with one output set only (where its LDS
 bank conflicts and time come from); spectra-rot: bench.py's cfg3 call, rotating over 4 distinct input
@@ -10,6 +10,8 @@ room: omega_room_modes over 512 resident spectra at K = 92 (16384-point) and K =
 and omega_room_decay over 8 resident histories of 122880 samples; one event pair per call, median / min / max.
 voice: omega_voice_features over 512 resident frames at the app's shape (K 1025, m 2048, float64 audio): the
 golden's `app` frames (tests/golden/voice.npz) repeated.
+waterfall: omega_waterfall_rows over 4096 resident frames (1025 bins, 853 cells; float32 and float64, with and without
+the RGB output) and omega_waterfall_colors over a 200 x 853 history; with --lib, another build of the same ABI.
 """
 import argparse
 import os
@@ -103,6 +105,62 @@ def voice(reps):
           f"{max(us):.1f}; {med / 512:.3f} us per frame)")
 
 
+def waterfall(reps):
+    """SpectrogramWaterfall's two device calls on resident inputs: omega_waterfall_rows over 4096 frames of 1025 bins
+    (853 cells) in float32 and float64, with and without the RGB output, and omega_waterfall_colors over a 200 x 853
+    history. Three passes of `reps` calls each between one event pair; the median pass, per call."""
+    import ctypes as C
+    from omega_gpu import SpectrogramWaterfall
+    from omega_gpu import _lib as L
+    lib = L.lib()
+    rng = np.random.default_rng(13)
+    F, n, lo, K = 4096, 1025, 1, 853
+    wf = SpectrogramWaterfall(48000)
+    eng = wf._eng
+    eng._check(lib.omega_waterfall_configure(eng._ctx, C.byref(L.WaterfallConfig(n, lo, K))))
+
+    def timed(label, call, moved):
+        for _ in range(5):
+            call()
+        torch.cuda.synchronize()
+        passes = []
+        for _ in range(3):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(reps):
+                call()
+            e.record()
+            e.synchronize()
+            passes.append(s.elapsed_time(e) * 1e3 / reps)
+        med = float(np.median(passes))
+        print(f"waterfall {label}: median {med:.1f} us per call (passes {', '.join(f'{v:.1f}' for v in passes)}); "
+              f"{moved / 1e6:.2f} MB moved = {moved / med / 1e3:.0f} GB/s")
+
+    amp = np.exp(rng.uniform(np.log(1e-4), np.log(10.0), (F, n)))
+    for dt in (torch.float32, torch.float64):
+        x = torch.from_numpy(amp).to(dt).cuda()
+        el = x.element_size()
+        stats = torch.empty(F, 7, dtype=torch.float64, device="cuda")
+        rows = torch.empty(F, K, dtype=dt, device="cuda")
+        rgb = torch.empty(F, K, 3, dtype=torch.uint8, device="cuda")
+        state = torch.empty(45, dtype=torch.float64, device="cuda")
+        eng._bind_stream(x)
+        for img in (None, rgb):
+            call = lambda: eng._check(lib.omega_waterfall_rows(  # noqa: E731
+                eng._ctx, x.data_ptr(), n, int(dt == torch.float64), F, 1, 0.0, 3, None, state.data_ptr(),
+                stats.data_ptr(), rows.data_ptr(), None if img is None else img.data_ptr(), L.MEM_DEVICE))
+            # the spectrum once, the dB row out and back in, the row out, the stats, the pixels
+            moved = F * (n * el + 3 * K * el + 7 * 8 + (3 * K if img is not None else 0))
+            timed(f"rows {str(dt).split('.')[1]} {'with' if img is not None else 'without'} rgb, F = {F}, cells = {K}",
+                  call, moved)
+        hist = rows[:200].contiguous()
+        out = torch.empty(200, K, 3, dtype=torch.uint8, device="cuda")
+        timed(f"colors {str(dt).split('.')[1]} 200 x {K}", lambda: eng._check(lib.omega_waterfall_colors(
+            eng._ctx, hist.data_ptr(), K, int(dt == torch.float64), 200, K, 3, out.data_ptr(), L.MEM_DEVICE)),
+            200 * K * (el + 3))
+    print("waterfall stats row 0:", stats[0].cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("stage")
@@ -118,6 +176,8 @@ def main():
         return room(a.reps)
     if a.stage == "voice":
         return voice(a.reps)
+    if a.stage == "waterfall":
+        return waterfall(a.reps)
     import bench
     from omega_gpu import NORTHSTAR_RESOLUTIONS, Engine
     from omega_gpu import _lib as L
