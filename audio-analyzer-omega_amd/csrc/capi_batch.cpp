@@ -1,6 +1,7 @@
 // libomega.so host side: the batch launch path -- omega_process_frames down to launch_batch, with the
-// meter segments and the stream layout -- and the meter, true-peak and weighting entry points that share
-// its state. This file enqueues; the arithmetic is in two pure headers: batch_plan.hpp's plan_batch lays
+// meter segments and the stream layout. (The entry points that measure level without the batch kernel
+// are capi_level.cpp's; what both files use is in omega_host below, declared in host.hpp.) This file
+// enqueues; the arithmetic is in two pure headers: batch_plan.hpp's plan_batch lays
 // out the grid of a call's shape, and meter_sync.hpp's step functions give every counter target of a
 // transition and the ledger (omega_ctx::ms) it leaves, on success and on a failed launch. enqueue_frames
 // decides the call's shape once (batch layout, meters in the grid, pipelined, overlapped) and hands the
@@ -12,7 +13,7 @@
 #include "batch_plan.hpp"
 #include "host.hpp"
 
-namespace {
+namespace omega_host __attribute__((visibility("hidden"))) {
 
 constexpr int kChunkFrames = kMeterChunk;
 
@@ -122,28 +123,6 @@ std::vector<MeterPrepParams> meter_chunks(const omega_ctx* c, const std::vector<
   return v;
 }
 
-// All meter chunks on one stream. tp_ready: when set, an event the true peaks of the batch wait on
-// (the prep kernels only read the LUFS_inst values, so they may start before it).
-int meters_enqueue(omega_ctx* c, const float* lufs, const float* tp, int64_t n_frames, double* out,
-                   hipStream_t stream, hipEvent_t tp_ready, unsigned* wait_ctr = nullptr, unsigned wait_target = 0) {
-  bool first = true;
-  const SyncStep st = step_state_chunks(c->ms, chunk_frames(n_frames));
-  c->ms = st.ok;
-  for (MeterPrepParams p : meter_chunks(c, st.chunks, lufs, tp, out)) {
-    // (wait_ctr: the first chunk's prep polls it before reading the batch's values -- the true peaks
-    // of omega_calculate_lufs on the side stream counting in, instead of an event join)
-    if (first && wait_ctr) {
-      p.wait_ctr = wait_ctr;
-      p.wait_target = wait_target;
-    }
-    HIPC(c, launch_meter_prep(p, stream));
-    if (tp_ready && first) HIPC(c, hipStreamWaitEvent(stream, tp_ready, 0));
-    HIPC(c, launch_meter_query(p, stream));
-    first = false;
-  }
-  return 0;
-}
-
 // Overlapped pipelined batches: order the last call's batch stream (batch, then meter segment) into the
 // context's stream. (The call before it was joined when the last one was enqueued.)
 int join_batches(omega_ctx* c) {
@@ -155,12 +134,9 @@ int join_batches(omega_ctx* c) {
   return 0;
 }
 
-}  // namespace
-
 // Meter pipelining: the pending meter segment as a launch of its own on the context's stream (the
 // stream of the batch it belongs to: omega_set_stream flushes before switching), or on `on` (an
 // overlapped call's batch stream); an overlapped call still on its batch stream is joined first.
-namespace omega_host __attribute__((visibility("hidden"))) {
 int flush_meters(omega_ctx* c, hipStream_t on) {
   if (!on)
     if (int e = join_batches(c)) return e;
@@ -276,12 +252,10 @@ int enqueue_batch_chunks(omega_ctx* c, const SpectralParams& sp, KWeightParams k
         p.wait_ctr = c->d_ctr + kCtrKw;
         p.wait_target = st.wait_target;
       }
-      HIPC(c, launch_meter_prep(p, c->fork[0]));
-      c->side_meters = true;
+      HIPC(c, launch_meter_prep(p, side_stream(c)));
       p.parts = 1;
       p.q_done = c->d_ctr + kCtrQuery;
-      HIPC(c, launch_meter_query(p, c->fork[0]));
-      c->side_meters = true;
+      HIPC(c, launch_meter_query(p, side_stream(c)));
     }
   }
   if (grid > 0) {
@@ -326,8 +300,7 @@ int enqueue_batch_direct(omega_ctx* c, SpectralParams sp, KWeightParams kp, Batc
   kp.kw_done = c->d_ctr + kCtrKw;
   p.wait_ctr = c->d_ctr + kCtrKw;
   p.wait_target = st.wait_target;
-  HIPC(c, launch_meter_prep(p, c->fork[0]));
-  c->side_meters = true;
+  HIPC(c, launch_meter_prep(p, side_stream(c)));
   MeterPrepParams mq = m0;
   mq.start_ctr = c->d_ctr + kCtrPrep;
   mq.start_target = st.start_target;
@@ -383,7 +356,6 @@ int enqueue_batch_pipelined(omega_ctx* c, const SpectralParams& sp, KWeightParam
   p.lufs_mirror = kp.lufs_mirror;
   p.mirror_gen = st.mirror_gen;
   if (tail) bp.tail_ctr = c->d_tail;
-  c->side_meters = true;
   // this call's segment, for the launch that runs it: it starts once the prep has counted in (its batch
   // has ended by then: no wait for the true peaks)
   MeterPrepParams mq = m0;
@@ -398,10 +370,10 @@ int enqueue_batch_pipelined(omega_ctx* c, const SpectralParams& sp, KWeightParam
   }
   c->ms = st.launched;
   if (tail) {
-    HIPC(c, hipStreamWaitValue32(c->fork[0], c->d_tail, st.tail_target, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    HIPC(c, hipStreamWaitValue32(side_stream(c), c->d_tail, st.tail_target, hipStreamWaitValueGte, 0xFFFFFFFFu));
     c->ms = st.waited;
   }
-  HIPC(c, launch_meter_prep(p, c->fork[0]));
+  HIPC(c, launch_meter_prep(p, side_stream(c)));
   c->ms = st.ok;
   c->pend_mq = mq;
   return 0;
@@ -491,20 +463,18 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
   if (do_kw) HIPC(c, launch_kweight(W, kp, s));
   std::vector<MeterPrepParams> mc;
   if (meters) {
-    const SyncStep st = step_state_chunks(c->ms, chunk_frames(n_frames));
-    // (a graph capture runs nothing: omega_process_frames takes the same step at each replay)
-    if (!(c->cap && s == c->cap)) c->ms = st.ok;
+    const SyncStep st = step_state_chunks(c->ms, chunk_frames(n_frames), true);
+    // (a graph capture runs nothing: the chunks' step is omega_process_frames', at each replay; the flag is set)
+    c->ms = c->cap && s == c->cap ? step_state_chunks(c->ms, {}, true).ok : st.ok;
     mc = meter_chunks(c, st.chunks, lufs, tp, meters);
     HIPC(c, hipEventRecord(c->ev_kw, s));
-    HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_kw, 0));
+    HIPC(c, hipStreamWaitEvent(side_stream(c), c->ev_kw, 0));
     for (MeterPrepParams p : mc) {
-      HIPC(c, launch_meter_prep(p, c->fork[0]));
-      c->side_meters = true;
+      HIPC(c, launch_meter_prep(p, side_stream(c)));
       p.parts = 1;
-      HIPC(c, launch_meter_query(p, c->fork[0]));
-      c->side_meters = true;
+      HIPC(c, launch_meter_query(p, side_stream(c)));
     }
-    HIPC(c, hipEventRecord(c->ev_join[0], c->fork[0]));
+    if (int e = side_join_record(c, 0)) return e;
   }
   if (do_res) HIPC(c, c->res_independent ? launch_mrfft_independent(sp, s) : launch_mrfft(sp, s));
   if (do_tp) HIPC(c, tp_launch(W, sp, s));
@@ -512,7 +482,7 @@ int enqueue_frames(omega_ctx* c, SpectralParams sp, KWeightParams kp, int W, int
     p.parts = 2;
     HIPC(c, launch_meter_query(p, s));
   }
-  if (meters) HIPC(c, hipStreamWaitEvent(s, c->ev_join[0], 0));
+  if (meters) return side_join_wait(c, 0, s);  // (the flag stays: the next counted omega_calculate_lufs joins again)
   return 0;
 }
 
@@ -552,24 +522,6 @@ int omega_dev_probe(omega_ctx* c, int which, const float* x, int64_t n_frames, f
   return e == hipSuccess ? 0 : fail(c, OMEGA_EHIP, "probe %d: %s", which, hipGetErrorString(e));
 }
 #endif
-
-int omega_meter_reset(omega_ctx* c) try {
-  if (!c) return OMEGA_EINVAL;
-  if (int e = flush_meters(c)) return e;  // (the pending segment reads the state being reset)
-  // a meter prep on the side stream may still be writing the next state after its count-in
-  if (c->fork[0]) HIPC(c, hipStreamSynchronize(c->fork[0]));
-  const int C = c->cfg.n_channels;
-  for (int b = 0; b < 2; ++b) {
-    HIPC(c, hipMemsetAsync(c->d_nl[b], 0, C * sizeof(int), c->stream));
-    HIPC(c, hipMemsetAsync(c->d_nt[b], 0, C * sizeof(int), c->stream));
-    HIPC(c, hipMemsetAsync(c->d_ns[b], 0, C * sizeof(int), c->stream));
-    HIPC(c, hipMemsetAsync(c->d_t0[b], 0, C * sizeof(uint32_t), c->stream));
-  }
-  HIPC(c, hipStreamSynchronize(c->stream));
-  return 0;
-} catch (...) {
-  return guard_fail(c);
-}
 
 int omega_process_frames(omega_ctx* c, const float* x, int64_t n_frames, int64_t frame_stride, int64_t channel_stride,
                          const omega_outputs* out, int mem) try {
@@ -718,372 +670,4 @@ int omega_process_stream(omega_ctx* c, const float* x, int64_t n_samples, int32_
 } catch (...) {
   return guard_fail(c);
 }
-
-int omega_true_peak(omega_ctx* c, const float* x, int64_t n, int32_t m, float* out_db, int mem) try {
-  return omega_true_peak_os(c, x, n, m, 4, out_db, mem);
-} catch (...) {
-  return guard_fail(c);
-}
-
-// Plan of the any-length transform: radices (4s, then 2, 3, 5, 7, then the remaining primes) and the
-// tables e^{-2 pi i m / N}, e^{2 pi i m / (4N)} in float64 rounded to float32
-int get_any_plan(omega_ctx* c, int N, omega_ctx::AnyPlan** out) {
-  auto it = c->any_plans.find(N);
-  if (it == c->any_plans.end()) {
-    omega_ctx::AnyPlan pl;
-    pl.radix = fft_radices(N);
-    if ((int)pl.radix.size() > kAnyMaxStages) return fail(c, OMEGA_EUNSUP, "length %d: too many factors", N);
-    std::vector<float2> tw(N), rot(3 * (N / 2) + 1);
-    for (int m = 0; m < N; ++m) tw[m] = make_float2((float)std::cos(2 * kPi * m / N), (float)-std::sin(2 * kPi * m / N));
-    for (size_t m = 0; m < rot.size(); ++m)
-      rot[m] = make_float2((float)std::cos(2 * kPi * (double)m / (4.0 * N)), (float)std::sin(2 * kPi * (double)m / (4.0 * N)));
-    int e = upload(c, &pl.tw, tw);
-    if (!e) e = upload(c, &pl.rot, rot);
-    if (!e && !pl.radix.empty() && pl.radix.back() > kAnyF32Radix) {
-      // a stage of R terms summed in float64 keeps its precision only with unrounded factors: the rounding
-      // errors of the float32 table add up over the R terms to the same offset in every output
-      e = upload(c, &pl.tw64, twiddles64(N, N));
-    }
-    if (e) return e;
-    it = c->any_plans.emplace(N, std::move(pl)).first;
-  }
-  *out = &it->second;
-  return 0;
-}
-
-// launches the any-length kernel over n frames in slices whose global scratch (N > kAnyLdsMax) stays
-// within 64 MiB; p.x / outputs advanced per slice
-int run_any(omega_ctx* c, AnyFftParams p, int truepeak) {
-  omega_ctx::AnyPlan* pl = nullptr;
-  if (int e = get_any_plan(c, p.N, &pl)) return e;
-  p.n_stages = (int)pl->radix.size();
-  for (int s = 0; s < p.n_stages; ++s) p.radix[s] = pl->radix[s];
-  p.tw = pl->tw;
-  p.tw64 = pl->tw64;
-  p.rot = pl->rot;
-  for (int ph = 0; ph < 4; ++ph) p.nyq_cos[ph] = (float)std::cos(kPi * ph / 4.0);
-  const int64_t n = p.n;
-  int64_t per = n;
-  if (p.N > kAnyLdsMax) {
-    per = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(8 << 20) / (3 * (int64_t)p.N)));
-    if (int e = grow(c, &c->d_any, &c->any_cap, per * 3 * p.N)) return e;
-    p.scratch = c->d_any;
-  }
-  const int nb = p.N / 2 + 1;
-  for (int64_t f0 = 0; f0 < n; f0 += per) {
-    AnyFftParams q = p;
-    q.x = p.x + f0 * p.frame_stride;
-    q.n = std::min(per, n - f0);
-    if (q.tp_out) q.tp_out = p.tp_out + f0;
-    if (q.mag) q.mag = p.mag + f0 * nb;
-    if (q.cplx) q.cplx = p.cplx + f0 * nb * 2;
-    HIPC(c, launch_any(q, truepeak, c->stream));
-  }
-  return 0;
-}
-
-int omega_true_peak_os(omega_ctx* c, const float* x, int64_t n, int32_t m, int32_t oversampling, float* out_db,
-                       int mem) try {
-  if (!c || !x || !out_db) return OMEGA_EINVAL;
-  if (oversampling != 1 && oversampling != 2 && oversampling != 4)
-    return fail(c, OMEGA_EUNSUP, "true peak: oversampling %d unsupported (1, 2, 4)", oversampling);
-  if (m < 1) return fail(c, OMEGA_EINVAL, "true peak: frame length %d", m);
-  if (n <= 0) return n == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
-  const bool any = !is_pow2_in(m, 512, 16384);
-  HIPC(c, hipSetDevice(c->device));
-  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
-  const float* dx = h.in(x, (size_t)n * m * sizeof(float));
-  float* dout = h.out(out_db, n, 3);
-  if (h.err) return h.err;
-  int e = 0;
-  if (any) {  // frames of other lengths (anyfft.hip)
-    AnyFftParams ap{};
-    ap.x = dx;
-    ap.frame_stride = m;
-    ap.n = n;
-    ap.N = m;
-    ap.phases = oversampling == 4 ? 0xE : (oversampling == 2 ? 0x4 : 0);
-    ap.tp_out = dout;
-    if ((e = run_any(c, ap, 1))) return e;
-    return h.finish();
-  }
-  SpectralParams sp = spectral_params(c);
-  sp.x = dx;
-  sp.C = 1;
-  sp.frame_stride = m;
-  sp.chan_stride = 0;
-  sp.n_cf = n;
-  sp.comb_out = nullptr;
-  for (int r = 0; r < kMaxRes; ++r) sp.res[r].mag_out = nullptr;
-  sp.n_res = 0;
-  sp.tp_out = dout;
-  float2* rot = nullptr;
-  e = get_rot(c, m, &rot);
-  if (e) return e;
-  sp.rot = rot;
-  sp.tp_phases = oversampling == 4 ? 0xE : (oversampling == 2 ? 0x4 : 0);
-  sp.tp_done = c->tp_count_to;  // (omega_calculate_lufs)
-  HIPC(c, tp_launch(m, sp, c->stream));
-  return h.finish();
-} catch (...) {
-  return guard_fail(c);
-}
-
-// the batch kernel's float32 K-weighting (kweight_kernel) on its own, for power-of-two frames
-int omega_k_weighting(omega_ctx* c, const float* x, int64_t n, int32_t m, float* weighted, float* lufs_inst,
-                      int mem) try {
-  if (!c || !x) return OMEGA_EINVAL;
-  if (!is_pow2_in(m, 512, 16384)) return fail(c, OMEGA_EUNSUP, "k-weighting: frame length %d unsupported", m);
-  if (n <= 0) return n == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
-  HIPC(c, hipSetDevice(c->device));
-  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
-  const float* dx = h.in(x, (size_t)n * m * sizeof(float));
-  float* dw = h.out(weighted, (size_t)n * m, 5);
-  float* dl = h.out(lufs_inst, n, 2);
-  if (h.err) return h.err;
-  int e = 0;
-  BiquadTab* tabs = nullptr;
-  if ((e = get_kw_tab(c, m, &tabs))) return e;
-  KWeightParams kp{dx, m, 0, 1, n, tabs, tabs + 1, dl, dw, OMEGA_WEIGHT_K};
-  HIPC(c, launch_kweight(m, kp, c->stream));
-  return h.finish();
-} catch (...) {
-  return guard_fail(c);
-}
-
-// The float64 filter cascade of a weighting mode for the context's sample rate
-// (professional_meters.py:48-72, :74-127): K = {butter(2, 38 Hz, high), iirfilter(2, 1500 Hz, high)}
-// blended 0.3; A = {butter(2, 20.598997, high), butter(1, 107.65265, high), butter(1, 737.86223, low),
-// butter(2, min(12194.217 / nyq, 0.99), low)} x 2.5; C = {butter(2, 20.598997, high), butter(2, 12194.217, low)}.
-W64Stage w64_stage(const BiquadCoef& q, int order) {
-  W64Stage s{};
-  s.b0 = q.b[0];
-  s.b1 = q.b[1];
-  s.b2 = q.b[2];
-  s.a1 = q.a[1];
-  s.a2 = q.a[2];
-  // scipy.signal.lfilter_zi: solve (I - companion(a).T) zi = b[1:] - a[1:] b[0]
-  const double B0 = s.b1 - s.a1 * s.b0, B1 = s.b2 - s.a2 * s.b0;
-  s.zi0 = (B0 + B1) / (1.0 + s.a1 + s.a2);
-  s.zi1 = B1 - s.a2 * s.zi0;
-  s.E = 3 * (order + 1);  // filtfilt's default padlen 3 max(len(a), len(b))
-  return s;
-}
-
-int get_w64_stages(omega_ctx* c, int mode, W64Stage** out) {
-  if (c->w64[mode]) {
-    *out = c->w64[mode];
-    return 0;
-  }
-  const double fs = c->cfg.sample_rate, nyq = fs / 2;
-  const double f1 = 20.598997, f2 = 107.65265, f3 = 737.86223, f4 = 12194.217;
-  const double f4c = std::min(f4 / nyq, 0.99) * nyq;
-  std::vector<W64Stage> t;
-  if (mode == OMEGA_WEIGHT_K)
-    t = {w64_stage(butter2(38.0, fs, true), 2), w64_stage(butter2(1500.0, fs, true), 2)};
-  else if (mode == OMEGA_WEIGHT_A)
-    t = {w64_stage(butter2(f1, fs, true), 2), w64_stage(butter1(f2, fs, true), 1),
-         w64_stage(butter1(f3, fs, false), 1), w64_stage(butter2(f4c, fs, false), 2)};
-  else
-    t = {w64_stage(butter2(f1, fs, true), 2), w64_stage(butter2(f4c, fs, false), 2)};
-  if (int e = upload(c, &c->w64[mode], t)) return e;
-  *out = c->w64[mode];
-  return 0;
-}
-
-int omega_weighting(omega_ctx* c, const float* x, int64_t n, int32_t m, int32_t mode, float* weighted,
-                    float* lufs_inst, int mem) try {
-  if (!c || !x) return OMEGA_EINVAL;
-  if (mode < OMEGA_WEIGHT_K || mode > OMEGA_WEIGHT_Z) return fail(c, OMEGA_EINVAL, "weighting mode %d", mode);
-  // scipy's filtfilt needs more samples than its padlen (9 for the first section of K, A and C)
-  if (m < 1 || (mode != OMEGA_WEIGHT_Z && m <= 9))
-    return fail(c, OMEGA_EINVAL, "weighting: the length of the input (%d) must be greater than padlen (9)", m);
-  if (n <= 0) return n == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
-  HIPC(c, hipSetDevice(c->device));
-  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
-  const float* dx = h.in(x, (size_t)n * m * sizeof(float));
-  float* dw = h.out(weighted, (size_t)n * m, 5);
-  float* dl = h.out(lufs_inst, n, 2);
-  if (h.err) return h.err;
-  int e = 0;
-  Weight64Params p{};
-  p.M = m;
-  p.mode = mode;
-  if (mode != OMEGA_WEIGHT_Z) {
-    if ((e = get_w64_stages(c, mode, &p.st))) return e;
-    p.n_st = mode == OMEGA_WEIGHT_A ? 4 : 2;
-  }
-  // float64 working buffers per frame: the signal and its odd extension (at most 64 MiB per launch)
-  p.scratch_stride = 2 * (int64_t)m + 32;
-  const int64_t per_launch = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)(8 << 20) / p.scratch_stride));
-  if ((e = grow(c, &c->d_w64, &c->w64_cap, per_launch * p.scratch_stride))) return e;
-  p.scratch = c->d_w64;
-  for (int64_t f0 = 0; f0 < n; f0 += per_launch) {
-    p.x = dx + f0 * m;
-    p.n = std::min(per_launch, n - f0);
-    p.weighted_out = dw ? dw + f0 * m : nullptr;
-    p.lufs_out = dl ? dl + f0 : nullptr;
-    HIPC(c, launch_weight64(p, c->stream));
-  }
-  return h.finish();
-} catch (...) {
-  return guard_fail(c);
-}
-
-// The meter aggregates on the caller's stream from device inputs. join_side: these kernels read the
-// state a meter prep on the side stream may still be writing (after its count-in), so the caller's
-// stream first waits for the side stream (a caller that has just joined it skips the second wait);
-// order_side: the next batch's meter prep runs on the side stream and reads, before its K-weighting
-// count, the state these kernels write, so the side stream is ordered after them (a host-memory
-// caller does it after its copies back, which then follow the kernels without an event between).
-int meter_update_dev(omega_ctx* c, const float* dl, const float* dt, int64_t n_frames, double* dm, bool join_side,
-                     bool order_side, unsigned* wait_ctr = nullptr, unsigned wait_target = 0) {
-  if (join_side) {
-    HIPC(c, hipEventRecord(c->ev_join[1], c->fork[0]));
-    HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[1], 0));
-  }
-  if (int e = meters_enqueue(c, dl, dt, n_frames, dm, c->stream, nullptr, wait_ctr, wait_target)) return e;
-  if (order_side) {
-    HIPC(c, hipEventRecord(c->ev_fork, c->stream));
-    HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_fork, 0));
-  }
-  return 0;
-}
-
-int omega_meter_update(omega_ctx* c, const float* lufs_inst, const float* tp_db, int64_t n_frames, double* meters,
-                       int mem) try {
-  if (!c || !lufs_inst || !tp_db || !meters) return OMEGA_EINVAL;
-  if (n_frames <= 0) return n_frames == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
-  if (int e = check_device_err(c)) return e;
-  HIPC(c, hipSetDevice(c->device));
-  if (int e = flush_meters(c)) return e;
-  const int64_t ncf = n_frames * c->cfg.n_channels;
-  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
-  const float* dl = h.in(lufs_inst, ncf * sizeof(float), 2);
-  const float* dt = h.in(tp_db, ncf * sizeof(float));
-  double* dm = h.out(meters, ncf * 5);
-  if (h.err) return h.err;
-  if (int e = meter_update_dev(c, dl, dt, n_frames, dm, true, true)) return e;
-  return h.finish();
-} catch (...) {
-  return guard_fail(c);
-}
-
-int omega_meter_load_history(omega_ctx* c, const float* lufs_inst, int64_t n_l, const float* tp_db, int64_t n_t,
-                             int mem) try {
-  if (!c) return OMEGA_EINVAL;
-  if (n_l < 0 || n_t < 0 || n_t > n_l) return fail(c, OMEGA_EINVAL, "need 0 <= n_t <= n_l");
-  if ((n_l && !lufs_inst) || (n_t && !tp_db)) return fail(c, OMEGA_EINVAL, "null history");
-  // rows older than the windows hold (integrated_len - 1 LUFS values, peak_len - 1 true peaks) leave no
-  // trace in the state a replay of them would build: keep the last ones (a time-shard exchange hands over
-  // up to 3599 / 59 rows whatever this context's window lengths are)
-  if (n_l > c->HL) {
-    lufs_inst += (n_l - c->HL) * (int64_t)c->cfg.n_channels;
-    n_l = c->HL;
-  }
-  if (n_t > std::min<int64_t>(c->HT, n_l)) {
-    const int64_t k = std::min<int64_t>(c->HT, n_l);
-    tp_db += (n_t - k) * (int64_t)c->cfg.n_channels;
-    n_t = k;
-  }
-  if (int e = check_device_err(c)) return e;
-  HIPC(c, hipSetDevice(c->device));
-  if (int e = flush_meters(c)) return e;  // (a pending segment reads the state being replaced)
-  const int C = c->cfg.n_channels;
-  const float* dl = lufs_inst;
-  const float* dt = tp_db;
-  if (mem == OMEGA_MEM_HOST) {  // (raw staging: a null history of no rows still gets its slot's pointer)
-    int e = stage_in(c, 2, lufs_inst, (size_t)n_l * C * sizeof(float), reinterpret_cast<const void**>(&dl));
-    if (!e) e = stage_in(c, 3, tp_db, (size_t)n_t * C * sizeof(float), reinterpret_cast<const void**>(&dt));
-    if (e) return e;
-  }
-  // as omega_meter_update: after the side stream's last writes of the state, and before its next reads
-  HIPC(c, hipEventRecord(c->ev_join[1], c->fork[0]));
-  HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[1], 0));
-  const int a = c->ms.cur;
-  MeterLoadParams p{dl, dt, (int)n_l, (int)n_t, C, c->HL, c->HT, (float)c->cfg.gate_lufs, c->d_hist_l[a],
-                    c->d_hist_t[a], c->d_nl[a], c->d_nt[a], c->d_skeys[a], c->d_ns[a], c->d_t0[a]};
-  HIPC(c, launch_meter_load(p, c->stream));
-  HIPC(c, hipEventRecord(c->ev_fork, c->stream));
-  HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_fork, 0));
-  if (mem == OMEGA_MEM_HOST) HIPC(c, hipStreamSynchronize(c->stream));
-  return 0;
-} catch (...) {
-  return guard_fail(c);
-}
-
-int omega_calculate_lufs(omega_ctx* c, const float* x, int64_t n_frames, int32_t m, int32_t mode, int32_t oversampling,
-                         float* lufs_inst, float* tp_db, double* meters, int mem) try {
-  if (!c || !x || !meters) return OMEGA_EINVAL;
-  if (n_frames <= 0) return n_frames == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
-  if (int e = check_device_err(c)) return e;
-  HIPC(c, hipSetDevice(c->device));
-  const int64_t ncf = n_frames * c->cfg.n_channels;
-  HostCall h(c, mem);  // (omega_process_frames' slots for the same data)
-  const float* dx = h.in(x, (size_t)ncf * m * sizeof(float));
-  float* dl = h.out(lufs_inst, ncf, 2);
-  float* dt = h.out(tp_db, ncf);
-  double* dm = h.out(meters, ncf * 5);
-  if (h.err) return h.err;
-  int e = 0;
-  // device scratch for the instantaneous values the caller does not want back
-  if (!dl || !dt) {
-    if ((e = grow(c, &c->d_lufs_scr, &c->lufs_scr_cap, 2 * ncf))) return e;
-    if (!dl) dl = c->d_lufs_scr;
-    if (!dt) dt = c->d_lufs_scr + ncf;
-  }
-  // The weighting and the true peak read the same input and write different outputs: the true peak
-  // runs on the side stream beside the weighting's latency-bound float64 scans (per-call metering of
-  // the app's 2048-sample frames: 37 + 14 us of kernels in sequence before). The aggregates read the
-  // meter state, which a meter prep on the side stream may still be writing, and the true peaks.
-  // Joining the side stream by an event costs ~5-10 us of idle GPU between kernels, so: when no meter
-  // kernel went to the side stream since the last join (the app's steady state: nothing but these
-  // calls; side_meters) there is nothing to join before, and the true peaks (power-of-two frames,
-  // direct launches) count themselves in on a device counter that the first meter prep polls before it
-  // reads them; otherwise events, as omega_meter_update.
-  const bool capture = c->cap && c->stream == c->cap;
-  const bool counted = !capture && is_pow2_in(m, 512, 16384);
-  if (counted && c->side_meters) {
-    HIPC(c, hipEventRecord(c->ev_join[1], c->fork[0]));
-    HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[1], 0));
-  }
-  c->side_meters = false;
-  HIPC(c, hipEventRecord(c->ev_fork, c->stream));
-  HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_fork, 0));
-  {
-    const hipStream_t main = c->stream;
-    c->stream = c->fork[0];
-    c->tp_count_to = counted ? c->d_ctr + kCtrLufsTp : nullptr;
-    e = omega_true_peak_os(c, dx, ncf, m, oversampling, dt, OMEGA_MEM_DEVICE);
-    c->tp_count_to = nullptr;
-    c->stream = main;
-    if (e) return e;
-  }
-  const SyncStep st = step_lufs_tp(c->ms, ncf);
-  if (counted) c->ms = st.ok;
-  if ((e = omega_weighting(c, dx, ncf, m, mode, nullptr, dl, OMEGA_MEM_DEVICE))) return e;
-  if (!counted) {
-    // the side stream's last work is the true peak, behind any earlier meter prep: one join serves
-    // both (omega_meter_update's second wait is skipped)
-    HIPC(c, hipEventRecord(c->ev_join[0], c->fork[0]));
-    HIPC(c, hipStreamWaitEvent(c->stream, c->ev_join[0], 0));
-  }
-  if ((e = flush_meters(c))) return e;
-  // for a host-memory call the side stream is ordered after the copies back (no event between the
-  // aggregates and the copies)
-  const bool host = mem == OMEGA_MEM_HOST;
-  if ((e = meter_update_dev(c, dl, dt, n_frames, dm, false, !host, counted ? c->d_ctr + kCtrLufsTp : nullptr,
-                            st.wait_target)))
-    return e;
-  if (host) {
-    if ((e = h.finish())) return e;
-    HIPC(c, hipEventRecord(c->ev_fork, c->stream));
-    HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_fork, 0));
-    return 0;
-  }
-  return 0;
-} catch (...) {
-  return guard_fail(c);
-}
-
 }  // extern "C"

@@ -542,9 +542,8 @@ int omega_set_stream(omega_ctx* c, void* s) try {
     // batch's K-weighting count, i.e. for a batch that started after the previous one ended. Across a
     // stream switch nothing orders them, so the new stream and fork[0] wait once for the old stream.
     HIPC(c, hipSetDevice(c->device));
-    HIPC(c, hipEventRecord(c->ev_fork, c->stream));
-    HIPC(c, hipStreamWaitEvent(ns, c->ev_fork, 0));
-    HIPC(c, hipStreamWaitEvent(c->fork[0], c->ev_fork, 0));
+    if (int e = after_main(c, ns)) return e;
+    HIPC(c, hipStreamWaitEvent(side_stream(c), c->ev_fork, 0));
     c->stream = ns;
     if (int e = side_stream_check(c)) return e;
   }

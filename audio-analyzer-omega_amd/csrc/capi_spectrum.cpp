@@ -68,7 +68,7 @@ int omega_rfft(omega_ctx* c, const float* x, int64_t n, int32_t m, int32_t windo
     ap.win = win;
     ap.mag = dm;
     ap.cplx = dc;
-    if ((e = run_any(c, ap, 0))) return e;
+    if ((e = run_any(c, ap, 0, c->stream))) return e;
     return h.finish();
   }
   RfftParams p{};

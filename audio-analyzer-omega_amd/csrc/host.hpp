@@ -280,11 +280,10 @@ struct omega_ctx {
   // aggregates on a side stream joined by events.
   int layout = 3;
   // the device counter words (meter_sync.hpp: MeterCounter) and the host's ledger of what was launched to
-  // count into them; every transition is a step function there, the table is in DESIGN.md §4
+  // count into them, with the side stream's unjoined-meter-work flag; every transition is a step function
+  // there, the table is in DESIGN.md §4
   unsigned* d_ctr = nullptr;
   MeterSync ms;
-  unsigned* tp_count_to = nullptr;  // set inside omega_calculate_lufs: its true peaks count in here
-  bool side_meters = false;  // meter kernels enqueued on fork[0] since omega_calculate_lufs last joined it
   // meter pipelining (omega_set_meter_pipelining): the params of the pending segment (MeterSync::pend)
   bool pipe = false;
   MeterPrepParams pend_mq{};
@@ -523,12 +522,45 @@ inline int get_savgol(omega_ctx* c, int w, const double** out) {
   });
 }
 
+// ---- the side stream (omega_ctx::fork[0]: the latency-bound meter kernels and omega_calculate_lufs' true
+// peak, beside the caller's stream) and its two event orders. Which way each orders reads off its name; the
+// ledger (MeterSync::side) records that a meter kernel went there and that the caller's stream joined it. ----
+inline hipStream_t side_stream(const omega_ctx* c) { return c->fork[0]; }
+// `waiter` runs after everything enqueued on the caller's stream so far (ev_fork)
+inline int after_main(omega_ctx* c, hipStream_t waiter) {
+  HIPC(c, hipEventRecord(c->ev_fork, c->stream));
+  HIPC(c, hipStreamWaitEvent(waiter, c->ev_fork, 0));
+  return 0;
+}
+inline int side_after_main(omega_ctx* c) { return after_main(c, side_stream(c)); }
+// The join, `s` after everything enqueued on the side stream so far (ev_join[slot]), in its two halves: the
+// back-to-back layout records early and waits behind its resolution and true-peak kernels
+inline int side_join_record(omega_ctx* c, int slot) {
+  HIPC(c, hipEventRecord(c->ev_join[slot], side_stream(c)));
+  return 0;
+}
+inline int side_join_wait(omega_ctx* c, int slot, hipStream_t s) {
+  HIPC(c, hipStreamWaitEvent(s, c->ev_join[slot], 0));
+  return 0;
+}
+inline int main_after_side(omega_ctx* c, int slot) {
+  if (int e = side_join_record(c, slot)) return e;
+  return side_join_wait(c, slot, c->stream);
+}
+
 // ---- tables and ordering shared by several families ----
 int get_window(omega_ctx* c, int m, int kind, float** out);  // capi_core.cpp
 int get_rot(omega_ctx* c, int M, float2** out);              // capi_core.cpp
 void drop_graphs(omega_ctx* c);                              // capi_core.cpp (the graph cache emptied)
-int flush_meters(omega_ctx* c, hipStream_t on = nullptr);    // capi_batch.cpp
 int tr_pow2_tables(omega_ctx* c, int n, const double2** tw, const double2** tw2);  // capi_time.cpp
+// capi_batch.cpp, shared with the level entry points of capi_level.cpp
+int flush_meters(omega_ctx* c, hipStream_t on = nullptr);
+int get_kw_tab(omega_ctx* c, int M, BiquadTab** out);
+hipError_t tp_launch(int W, const SpectralParams& sp, hipStream_t s);
+SpectralParams spectral_params(omega_ctx* c);
+std::vector<int64_t> chunk_frames(int64_t n_frames);
+std::vector<MeterPrepParams> meter_chunks(const omega_ctx* c, const std::vector<ChunkSync>& chunks, const float* lufs,
+                                          const float* tp, double* out);
 
 // ---- host-memory staging (inline: omega_process_frames calls these on every step) ----
 // Page-locked host buffer of at least `bytes` (grown on demand; hipHostMalloc).
@@ -782,8 +814,8 @@ int chained_frame_chunks(omega_ctx* c, double* (&blob)[2], size_t blob_len, size
 
 }  // namespace omega_host
 
-// the any-length transform's plan and launches (capi_batch.cpp), shared by omega_true_peak_os and omega_rfft
+// the any-length transform's plan and launches on `s` (capi_level.cpp), shared by omega_true_peak_os and omega_rfft
 extern "C" {
 int get_any_plan(omega_ctx* c, int N, omega_ctx::AnyPlan** out);
-int run_any(omega_ctx* c, AnyFftParams p, int truepeak);
+int run_any(omega_ctx* c, AnyFftParams p, int truepeak, hipStream_t s);
 }

@@ -3,12 +3,14 @@
 // targets and the whole ledger after the outcome the line names, one step per line.
 //   Z                                     -> MeterSync{} (configure)
 //   S v                                   -> every count := v (the six, seg_par, mirror_gen, tail)
-//   B k f1..fk ok                         -> step_state_chunks (back-to-back layout, meters_enqueue, graph replay)
+//   B k f1..fk ok                         -> step_state_chunks (meters_enqueue, graph replay)
+//   E k f1..fk ok                         -> step_state_chunks, on the side stream (back-to-back layout)
 //   K n_cf C k f1..fk ok|fail             -> step_chunks
 //   D n_cf C ok|fail                      -> step_direct
 //   P n_cf C tail ok|fail|launched|waited -> step_pipelined
 //   F ok|fail                             -> step_flush
-//   L n_cf ok|fail                        -> step_lufs_tp
+//   L n_cf counted ok|fail                -> step_lufs_tp
+//   J ok|fail                             -> step_join
 // No device and no context: the header is integer arithmetic only.
 #include <cinttypes>
 #include <cstdio>
@@ -57,6 +59,8 @@ int main() {
       outcome = false;
     } else if (kind == 'B') {
       st = step_state_chunks(m, read_frames());
+    } else if (kind == 'E') {
+      st = step_state_chunks(m, read_frames(), true);
     } else if (kind == 'K') {
       if (std::scanf("%" SCNd64 " %d", &n, &C) != 2) return 2;
       st = step_chunks(m, n, C, read_frames());
@@ -69,8 +73,10 @@ int main() {
     } else if (kind == 'F') {
       st = step_flush(m);
     } else if (kind == 'L') {
-      if (std::scanf("%" SCNd64, &n) != 1) return 2;
-      st = step_lufs_tp(m, n);
+      if (std::scanf("%" SCNd64 " %d", &n, &C) != 2) return 2;
+      st = step_lufs_tp(m, n, C != 0);
+    } else if (kind == 'J') {
+      st = step_join(m);
     } else {
       return 2;
     }
@@ -87,16 +93,16 @@ int main() {
       else if (std::strcmp(word, "ok"))
         return 2;
     }
-    std::printf("wait=%u start=%u join=%u tail_target=%u gen=%u q_n=%d", st.wait_target, st.start_target, st.join_target,
-                st.tail_target, st.mirror_gen, st.q_n);
+    std::printf("wait=%u start=%u join=%u tail_target=%u gen=%u q_n=%d join_side=%d", st.wait_target, st.start_target,
+                st.join_target, st.tail_target, st.mirror_gen, st.q_n, st.join_side ? 1 : 0);
     list("frames", st.chunks, [](const ChunkSync& c) { return c.n_frames; });
     list("par", st.chunks, [](const ChunkSync& c) { return c.par; });
     list("seg_pre", st.chunks, [](const ChunkSync& c) { return c.seg_pre_target; });
     list("seg_post", st.chunks, [](const ChunkSync& c) { return c.seg_post_target; });
     std::printf(" kw=%u query=%u tp=%u prep=%u seg=%u lufs_tp=%u seg_par=%u,%u cur=%d pend=%d pend_nq=%d pend_par=%d"
-                " mirror_gen=%u tail=%u\n",
+                " mirror_gen=%u tail=%u side=%d\n",
                 m.kw, m.query, m.tp, m.prep, m.seg, m.lufs_tp, m.seg_par[0], m.seg_par[1], m.cur, m.pend ? 1 : 0,
-                m.pend_nq, m.pend_par, m.mirror_gen, m.tail);
+                m.pend_nq, m.pend_par, m.mirror_gen, m.tail, m.side ? 1 : 0);
   }
   return 0;
 }

@@ -408,6 +408,71 @@ def test_calculate_lufs_interleaved_with_batches():
         np.testing.assert_array_equal(a, b)
 
 
+def test_calculate_lufs_refused_calls_leave_the_next_call_right():
+    """A batch whose meter prep went to the side stream, then two omega_calculate_lufs calls the library
+    refuses (oversampling 3; frames of 9 samples in mode K: scipy's padlen), then three good ones on
+    2048-sample frames: the refusals keep their error class and text, change no meter state and leave the
+    side stream unjoined-but-marked, so every output equals, bitwise, a context that ran the batch and the
+    good calls alone with the host synchronised after each. What this cannot do: where a refused call
+    wrongly marked the side stream joined, the next call's aggregates only raced the batch's prep, and this
+    test does not reliably lose that race. The rule itself -- only a join clears the mark, a call that ends
+    before its join leaves it -- is pinned on the CPU (tests/test_meter_sync.py)."""
+    import torch
+    from omega_gpu import Engine, NORTHSTAR_RESOLUTIONS
+    from omega_gpu._lib import OmegaError, UnsupportedError
+    xb = torch.from_numpy(S.cfg2_batch(16, seed_l=31, seed_r=32)).cuda()
+    rng = np.random.default_rng(33)
+    xs = (0.2 * rng.standard_normal((3, 2, 2048))).astype(np.float32)
+    res = []
+    for refused in (True, False):
+        eng = Engine(NORTHSTAR_RESOLUTIONS, FS, 20000, target_bins=512, n_channels=2)
+        o = eng.process_frames(xb, 16, 2 * 16384, 16384, meters=True)
+        outs = [o[k] for k in sorted(o)]
+        if refused:
+            with pytest.raises(UnsupportedError) as err:
+                eng.calculate_lufs(xs[0], "K", oversampling=3)
+            assert str(err.value) == "libomega error -4: true peak: oversampling 3 unsupported (1, 2, 4)"
+            with pytest.raises(OmegaError) as err:
+                eng.calculate_lufs(xs[0][:, :9], "K")
+            assert type(err.value) is OmegaError
+            assert str(err.value) == ("libomega error -1: weighting: the length of the input (9) must be greater "
+                                      "than padlen (9)")
+        else:
+            eng.synchronize()
+            torch.cuda.synchronize()
+        for k in range(3):
+            outs.extend(eng.calculate_lufs(xs[k], "K"))
+            if not refused:
+                eng.synchronize()
+        eng.synchronize()
+        torch.cuda.synchronize()
+        res.append([v.cpu().numpy() if hasattr(v, "cpu") else v for v in outs])
+    assert len(res[0]) == len(res[1]) == 4 + 9
+    for a, b in zip(*res):
+        np.testing.assert_array_equal(a, b)
+
+
+def test_calculate_lufs_grows_the_any_length_scratch():
+    """Frames of 6860 = 4 * 5 * 7^3 samples, past the 6826-sample limit of the LDS transform: the true peak
+    of omega_calculate_lufs, on the side stream, runs through the any-length transform's global scratch,
+    which the second call (4 stereo frames after 1) replaces by a larger one. Both calls give bitwise what
+    omega_weighting, omega_true_peak_os and omega_meter_update give on a second context."""
+    from omega_gpu import Engine, Resolution
+    rng = np.random.default_rng(41)
+    kw = dict(sample_rate=FS, max_freq=20000, target_bins=2, frame_size=512, n_channels=2)
+    e1 = Engine([Resolution((20, 20000), 512, 256, 1.0)], **kw)
+    e2 = Engine([Resolution((20, 20000), 512, 256, 1.0)], **kw)
+    for n_frames in (1, 4):
+        x = (0.2 * rng.standard_normal((n_frames * 2, 6860))).astype(np.float32)
+        li, tp, met = e1.calculate_lufs(x, "K")
+        _, li2 = e2.weighting(x, "K", weighted=False)
+        tp2 = e2.true_peak(x)
+        met2 = e2.meter_update(li2, tp2, n_frames)
+        np.testing.assert_array_equal(li, li2)
+        np.testing.assert_array_equal(tp, tp2)
+        np.testing.assert_array_equal(met, met2)
+
+
 def test_meter_too_short_keeps_state():
     """A frame of 9 samples or fewer (scipy's filtfilt raises: padlen 9) is logged and the meters keep
     their state; 480 samples (not a power of two) is metered like the reference."""

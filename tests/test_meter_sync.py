@@ -6,7 +6,10 @@ to wrap, then long seeded sequences that mix every path with failed batch launch
 orders the kernels rely on are checked in the device's own wrap-aware comparison: nothing waits for work
 that was never launched, a failed pipelined launch or flush changes nothing, a failed direct or chunked
 launch publishes the K-weighting count the prep waits for, the mirror parities alternate, the pending
-segment keeps its size, and a flush leaves no segment target ahead of the segment count."""
+segment keeps its size, and a flush leaves no segment target ahead of the segment count. The side flag
+(MeterSync::side: a meter kernel is on the side stream, unjoined) follows the same traces: only a step that
+enqueues there sets it, only the join step clears it, a counted omega_calculate_lufs is told to join exactly
+when such a step came since the last join, and a call that ends before its join leaves it set."""
 import os
 import random
 import subprocess
@@ -73,14 +76,39 @@ def _reached(issued, target):
     return M.sdiff(issued, target) >= 0
 
 
+def _on_side(w):
+    """the line's step enqueued (or may have enqueued) a meter prep or LUFS query on the side stream: chunked
+    with chunks and direct whatever the batch launch did, the back-to-back layout, pipelined unless its
+    launch failed"""
+    return (w[0] == "K" and int(w[3]) > 0) or w[0] in ("D", "E") or (w[0] == "P" and w[-1] != "fail")
+
+
 def _assert_invariants(trace):
-    last_par = None   # mirror parity of the last successful pipelined step of this context
+    last_par = None   # mirror parity of the last pipelined launch of this context
     pend_n_cf = None  # n_cf of the step that set the pending segment
+    dirty = False     # a step enqueued on the side stream since the last join step
     for i, (ln, t, before, after) in enumerate(trace):
         w = ln.split()
         kind, good, what = w[0], w[-1] == "ok", (i, ln)
         if kind == "Z":
             last_par = pend_n_cf = None
+            dirty = False
+        # the side flag: set only by a step that enqueues on the side stream -- in every outcome of it, the
+        # failed, launched and waited ones included -- and cleared only by the join step
+        if _on_side(w):
+            dirty = True
+            assert after["side"] == 1, what
+        elif kind == "J" and good:
+            dirty = False
+            assert after["side"] == 0, what
+        elif kind not in "ZS":
+            assert after["side"] == before["side"], what
+        assert after["side"] == int(dirty), what
+        # a counted omega_calculate_lufs skips its join only when nothing went to the side stream since the last
+        if kind == "L":
+            assert t["join_side"] == int(bool(int(w[2])) and dirty), what
+            if int(w[2]) and not t["join_side"]:
+                assert not dirty, what
         # nothing waits for work that was never launched: every target against its counter's issued count,
         # once the step that enqueues the awaited workgroups has committed
         if kind in ("K", "D"):          # (the prep is enqueued and waits even when the batch launch fails)
@@ -100,13 +128,14 @@ def _assert_invariants(trace):
         if good or kind == "K":
             for pre, post in zip(t["seg_pre"], t["seg_post"]):
                 assert _reached(after["seg"], pre) and _reached(after["seg"], post), what
-        # a failed pipelined launch or flush: bit-equal
-        if kind in ("P", "F") and not good:
-            assert after == before, what
-        if kind == "P" and good:
+        # a failed pipelined launch or flush: bit-equal, the side flag included
+        if kind in ("P", "F") and w[-1] == "fail":
+            assert after == before and after["side"] == before["side"], what
+        if kind == "P" and w[-1] != "fail":   # (launched, waited: the batch ran with this generation too)
             assert t["gen"] != 0 and after["mirror_gen"] == t["gen"], what
             assert last_par is None or (t["gen"] & 1) != last_par, what
             last_par = t["gen"] & 1
+        if kind == "P" and good:
             pend_n_cf = int(w[1])
         if after["pend"]:
             assert after["pend_nq"] == M.meter_segment_wgs(pend_n_cf), what
@@ -132,7 +161,9 @@ def _table():
             for C in CH:
                 for res in ("ok", "fail"):
                     lines += start + [f"D {n} {C} {res}"]
-                    lines += start + [f"L {n} {res}"]
+                    for counted in (0, 1):
+                        lines += start + [f"L {n} {counted} {res}"]
+                        lines += start + [f"D {n} {C} ok", f"L {n} {counted} {res}", f"J {res}", f"L {n} {counted} {res}"]
                     for fr in FRAMES:
                         lines += start + [f"K {n} {C} {_fr(fr)} {res}"]
                 for tail in (0, 1):
@@ -143,6 +174,7 @@ def _table():
                     lines += start + [f"P {n} {C} 1 ok", f"F {res}"]
         for fr in FRAMES:
             lines += start + [f"B {_fr(fr)} ok"]
+            lines += start + [f"E {_fr(fr)} ok", "J fail", f"B {_fr(fr)} ok", "J ok", f"E {_fr(fr)} ok"]
             lines += start + ["P 512 2 1 ok", "F ok", f"B {_fr(fr)} ok", f"B {_fr(fr)} ok"]
         lines += start + ["F ok"] + start + ["F fail"]
         lines += start + ["P 9 2 1 ok"] * 4 + ["F ok"]   # (from 2^32 - 3: the generation crosses 0xFFFFFFFF -> 2)
@@ -153,6 +185,7 @@ def test_step_tables_match_the_model(dump):
     lines = _table()
     got, want = dump(lines), _model(lines)
     _assert_same(lines, got, want)
+    _assert_invariants(_trace(lines, got))   # (every outcome of every step: the side flag's rules above all)
     # from 2^32 - 3 a step that adds 3 or more to a count takes it, and its target, past the wrap
     for i, ln in enumerate(lines):
         if ln.startswith("S ") and lines[i + 1].split()[0] in "DK" and int(lines[i + 1].split()[1]) >= 7:
@@ -163,7 +196,7 @@ def test_step_tables_match_the_model(dump):
 def test_steps_by_hand(dump):
     """a few rows worked out from the rules by hand, so the header and the model cannot agree on a wrong rule"""
     got = dump(["Z", "D 8 2 ok", "P 9 1 1 ok", "P 512 2 1 ok", "F ok", "K 8192 2 2 2048 1 fail",
-                f"S {2 ** 32 - 1}", "P 8 2 0 ok", "L 3 ok"])
+                f"S {2 ** 32 - 1}", "P 8 2 0 ok", "L 3 1 ok", "L 3 0 ok", "J ok", "L 3 1 ok", "E 1 5 ok"])
     t, m = got[1]   # direct, 8 channel-frames of 2 channels: one meter workgroup
     assert (t["wait"], t["start"], t["join"], t["q_n"], t["par"], t["seg_pre"], t["seg_post"]) == (8, 2, 8, 1, [0], [0], [0])
     assert (m["kw"], m["tp"], m["prep"], m["seg"], m["seg_par"], m["cur"]) == (8, 8, 2, 1, [1, 0], 1)
@@ -180,8 +213,34 @@ def test_steps_by_hand(dump):
     assert (m["kw"], m["query"], m["cur"]) == (8200, 1026, 1)
     t, m = got[7]   # the generation after 0xFFFFFFFF is 2; prep 2^32 - 1 + 2 wraps to 1
     assert (t["gen"], t["start"], m["prep"], m["tail"]) == (2, 1, 1, 2 ** 32 - 1)
-    t, m = got[8]
-    assert (t["wait"], m["lufs_tp"]) == (2, 2)
+    assert [m["side"] for _, m in got[:9]] == [0, 1, 1, 1, 1, 1, 1, 1, 1]   # (a flush is no join; S keeps it)
+    t, m = got[8]   # counted true peaks behind batches: they count in, and the call is told to join first
+    assert (t["wait"], t["join_side"], m["lufs_tp"], m["side"]) == (2, 1, 2, 1)
+    t, m = got[9]   # not counted: no counter moves, no join before (it joins behind its true peak)
+    assert (t["join_side"], m["lufs_tp"], m["side"]) == (0, 2, 1)
+    t, m = got[11]  # after the join: nothing to join
+    assert (got[10][1]["side"], t["wait"], t["join_side"], m["lufs_tp"], m["side"]) == (0, 5, 0, 5, 0)
+    t, m = got[12]  # the back-to-back layout: no counter, one chunk, the side stream used again
+    assert (t["par"], m["cur"], m["side"], m["lufs_tp"]) == ([0], 1, 1, 5)
+
+
+def test_a_call_that_ends_before_its_join_keeps_the_side_flag(dump):
+    """omega_calculate_lufs behind a batch whose prep went to the side stream: a call that ends early -- refused,
+    or a failed launch -- takes no join step, so the flag stays and the next counted call still joins first"""
+    lines = ["Z", "D 32 2 ok",
+             "L 4 0 ok",            # frames of another length: the true peak went out, the weighting failed: no join
+             "L 4 1 fail",          # counted: the join's event record failed (no J), or the true-peak launch
+             "L 4 1 fail", "J ok", "L 4 1 ok", "B 1 2 ok",   # a whole counted call: told to join, joins, counts in
+             "L 4 1 ok", "B 1 2 ok",                         # the steady state: nothing to join
+             "P 32 2 1 fail", "L 4 1 ok", "F ok", "B 1 2 ok",   # a failed pipelined launch put nothing there
+             "P 32 2 1 launched", "L 4 1 fail"]              # one that failed after its launch may have
+    got, want = dump(lines), _model(lines)
+    _assert_same(lines, got, want)
+    _assert_invariants(_trace(lines, got))
+    side = [m["side"] for _, m in got]
+    join = [t["join_side"] for t, _ in got]
+    assert side == [0, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1]
+    assert [join[i] for i in (2, 3, 4, 6, 8, 11, 15)] == [0, 1, 1, 0, 0, 0, 1]
 
 
 # ---- sequences ----
@@ -189,41 +248,61 @@ def test_steps_by_hand(dump):
 def _sequence(rng, near_wrap):
     """200 steps of one context as the entry points drive it: a pending segment is flushed before any
     step but a pipelined one (a failed flush ends the call: the step is not taken); each batch launch and
-    each flush fails with probability 0.1"""
+    each flush fails with probability 0.1. omega_calculate_lufs (L), counted or not: the join step first where
+    the model's step says so, the true peaks, the join of the uncounted path, the flush, the chunks of
+    meters_enqueue -- and with probability 0.1 each the call ends before its join or at its true-peak launch.
+    E: the back-to-back layout, its chunks on the side stream."""
     lines = ["Z"]
+    led = [M.zero()]   # the model's ledger after the lines so far: what the entry point reads its join from
+
+    def emit(ln):
+        lines.append(ln)
+        led[0] = M.step(led[0], ln)[1]
+
     if near_wrap:   # (within 40: the counts that grow by one or two per step -- generation, tail, prep -- wrap too)
-        lines.append(f"S {2 ** 32 - rng.randint(1, rng.choice((40, 3000)))}")
+        emit(f"S {2 ** 32 - rng.randint(1, rng.choice((40, 3000)))}")
     tail = rng.randint(0, 1)
     pend = False
     while len(lines) < 200:
         res = "fail" if rng.random() < 0.1 else "ok"
         C = rng.choice(CH)
         n = C * rng.choice((1, 3, 4, 5, 256, 511, 512, 2048))
-        kind = rng.choices("PDFKBLZ", (35, 20, 10, 10, 10, 10, 2))[0]
-        if kind == "L":     # the counted true peaks go first, then the flush, then the chunks of meters_enqueue
-            lines.append(f"L {n} {res}")
+        kind = rng.choices("PDFKBLZE", (35, 20, 10, 10, 10, 10, 2, 5))[0]
+        if kind == "L":     # the true peaks go first, then the flush, then the chunks of meters_enqueue
+            counted = rng.randint(0, 1)
+            if M.lufs_tp(led[0], n, counted)[0]["join_side"]:
+                if rng.random() < 0.1:   # (the join's event record or wait failed: the call ends, no step taken)
+                    continue
+                emit("J ok")
+            emit(f"L {n} {counted} {res}")
             if res == "fail":
                 continue
+            if not counted:
+                if rng.random() < 0.1:   # (the weighting refused or failed: no join)
+                    continue
+                emit("J ok")
         if kind != "P" and kind != "Z" and pend:
             fres = "fail" if rng.random() < 0.1 else "ok"
-            lines.append(f"F {fres}")
+            emit(f"F {fres}")
             if fres == "fail":
                 continue
             pend = False
         if kind == "P":
-            lines.append(f"P {n} {C} {tail} {res}")
+            if res == "ok" and rng.random() < 0.1:   # (the tail wait or the prep launch failed)
+                res = rng.choice(("launched", "waited"))
+            emit(f"P {n} {C} {tail} {res}")
             pend = pend or res == "ok"
         elif kind == "D":
-            lines.append(f"D {n} {C} {res}")
+            emit(f"D {n} {C} {res}")
         elif kind == "K":
             k = rng.randint(2, 4)
             fr = [2048] * (k - 1) + [rng.randint(1, 2048)]
-            lines.append(f"K {sum(fr) * C} {C} {_fr(fr)} {res}")
-        elif kind in "BL":
+            emit(f"K {sum(fr) * C} {C} {_fr(fr)} {res}")
+        elif kind in "BLE":
             fr = [2048] * rng.randint(0, 2) + [rng.randint(1, 2048)]
-            lines.append(f"B {_fr(fr)} ok")
+            emit(f"{'E' if kind == 'E' else 'B'} {_fr(fr)} ok")
         elif kind == "Z":
-            lines.append("Z")
+            emit("Z")
             pend = False
     return lines[:200]
 
@@ -233,7 +312,11 @@ def test_sequences_match_the_model_and_keep_the_orders(dump):
     seqs = [_sequence(rng, near_wrap=bool(s & 1)) for s in range(300)]
     lines = [ln for sq in seqs for ln in sq]
     kinds = {ln.split()[0] + ln.split()[-1] for ln in lines}
-    assert {"Pok", "Pfail", "Dok", "Dfail", "Fok", "Ffail", "Kok", "Kfail", "Bok", "Lok"} <= kinds
+    assert {"Pok", "Pfail", "Plaunched", "Pwaited", "Dok", "Dfail", "Fok", "Ffail", "Kok", "Kfail", "Bok", "Eok",
+            "Lok", "Lfail", "Jok"} <= kinds
+    for counted in (0, 1):   # both values of counted, and counted calls with and without a join before them
+        assert any(ln.startswith("L ") and int(ln.split()[2]) == counted for ln in lines)
+    assert any(a == "J ok" and b.split()[0] == "L" and b.split()[2] == "1" for a, b in zip(lines, lines[1:]))
     got, want = dump(lines), _model(lines)   # (every sequence starts with Z: one run serves them all)
     _assert_same(lines, got, want)
     wraps = sum(1 for ln, (_, m), (_, b) in zip(lines[1:], got[1:], got) if ln != "Z" and m["kw"] < b["kw"])
