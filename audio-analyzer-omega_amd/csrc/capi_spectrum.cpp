@@ -304,10 +304,10 @@ int omega_bands_apply(omega_ctx* c, omega_bands* b, const float* spec, int64_t n
   return guard_fail(c);
 }
 
-int omega_chroma(omega_ctx* c, const float* spec, int64_t n, int32_t n_bins, double df, double* out_raw, int mem) try {
-  if (!c || !spec || !out_raw || n_bins < 3 || !(df > 0)) return OMEGA_EINVAL;
-  if (n <= 0) return n == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
-  HIPC(c, hipSetDevice(c->device));
+}  // extern "C"
+
+namespace omega_host {
+int get_chroma_mat(omega_ctx* c, int n_bins, double df, ChromaMat* out) {
   auto it = c->chroma_mats.find(n_bins);
   if (it == c->chroma_mats.end() || c->chroma_df != df) {
     // chromagram.py:122-146 with transposition offset 0: bins 20 < f < 8000
@@ -337,12 +337,24 @@ int omega_chroma(omega_ctx* c, const float* spec, int64_t n, int32_t n_bins, dou
     c->chroma_df = df;
     it = c->chroma_mats.find(n_bins);
   }
+  *out = {it->second.first, it->second.second.first, it->second.second.second};
+  return 0;
+}
+}  // namespace omega_host
+
+extern "C" {
+
+int omega_chroma(omega_ctx* c, const float* spec, int64_t n, int32_t n_bins, double df, double* out_raw, int mem) try {
+  if (!c || !spec || !out_raw || n_bins < 3 || !(df > 0)) return OMEGA_EINVAL;
+  if (n <= 0) return n == 0 ? 0 : fail(c, OMEGA_EINVAL, "negative count");
+  HIPC(c, hipSetDevice(c->device));
+  ChromaMat m{};
+  if (int e = get_chroma_mat(c, n_bins, df, &m)) return e;
   HostCall h(c, mem);
   const float* ds = h.in(spec, (size_t)n * n_bins * sizeof(float));
   double* dout = h.out(out_raw, (size_t)n * 12);
   if (h.err) return h.err;
-  HIPC(c, launch_chroma(ds, n, n_bins, it->second.second.first, it->second.second.second, it->second.first, dout,
-                        c->stream));
+  HIPC(c, launch_chroma(ds, n, n_bins, m.lo, m.hi, m.mat, dout, c->stream));
   return h.finish();
 } catch (...) {
   return guard_fail(c);

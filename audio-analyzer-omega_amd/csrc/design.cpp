@@ -320,4 +320,56 @@ void np_leaves(int off, int n, int depth, std::vector<unsigned>& out) {
   np_leaves(off + n2, n - n2, depth - 1, out);
 }
 
+// ---- ChromagramAnalyzer's genre tables (chromagram.py:31-68) ----
+namespace {
+const double kKrumhansl[2][12] = {{6.35, 2.23, 3.48, 2.33, 4.38, 4.09, 2.52, 5.19, 2.39, 3.66, 2.29, 2.88},
+                                  {6.33, 2.68, 3.52, 5.38, 2.60, 3.53, 2.54, 4.75, 3.98, 2.69, 3.34, 3.17}};
+// major_weights, minor_weights per profile: pop, jazz, classical, metal, rock
+const double kGenreWeights[5][2][12] = {
+    {{1.5, 0.5, 1.0, 0.5, 1.2, 1.0, 0.5, 1.2, 0.5, 1.0, 0.5, 0.8}, {1.5, 0.6, 1.0, 1.2, 0.6, 1.0, 0.6, 1.2, 1.0, 0.6, 1.0, 0.8}},
+    {{1.0, 0.8, 1.0, 0.9, 1.0, 1.0, 0.9, 1.0, 0.8, 1.0, 0.8, 1.0}, {1.0, 0.8, 1.0, 1.0, 0.9, 1.0, 0.8, 1.0, 1.0, 0.9, 1.0, 0.9}},
+    {{1.2, 0.7, 1.0, 0.7, 1.1, 1.0, 0.7, 1.1, 0.7, 1.0, 0.7, 0.9}, {1.2, 0.8, 1.0, 1.1, 0.8, 1.0, 0.8, 1.1, 1.0, 0.8, 1.0, 0.9}},
+    {{1.8, 0.4, 1.2, 0.4, 1.0, 1.2, 0.6, 1.4, 0.4, 1.0, 0.4, 0.6}, {1.8, 0.6, 1.2, 1.4, 0.5, 1.2, 0.5, 1.4, 1.2, 0.5, 1.2, 0.7}},
+    {{1.6, 0.5, 1.1, 0.5, 1.1, 1.1, 0.6, 1.3, 0.5, 1.0, 0.5, 0.7}, {1.6, 0.6, 1.1, 1.3, 0.6, 1.1, 0.6, 1.3, 1.1, 0.6, 1.1, 0.8}}};
+const double kGenreTolerance[5] = {0.2, 0.8, 0.3, 0.6, 0.4};
+int genre_profile(int genre) { return genre >= 0 && genre < 5 ? genre : 0; }
+// np.add.reduce over 12 contiguous float64 values
+double np_sum12(const double* a) {
+  double r = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+  for (int i = 8; i < 12; ++i) r += a[i];
+  return r;
+}
+}  // namespace
+
+double tonal_blend(int genre) {
+  return genre == OMEGA_TONAL_METAL || genre == OMEGA_TONAL_ROCK ? 0.7 : (genre == OMEGA_TONAL_JAZZ ? 0.5 : 0.3);
+}
+double tonal_tolerance(int genre) { return kGenreTolerance[genre_profile(genre)]; }
+
+std::vector<double> tonal_table(int genre) {
+  const double(&W)[2][12] = kGenreWeights[genre_profile(genre)];
+  std::vector<double> t(kTnTabLen, 0.0);
+  for (int root = 0; root < 12; ++root)
+    for (int minor = 0; minor < 2; ++minor) {
+      const int k = 2 * root + minor;
+      double* key = &t[kTnTabKey + k * 12];
+      double* alt = &t[kTnTabAlt + k * 12];
+      for (int j = 0; j < 12; ++j) {  // np.roll(v, root)[j] = v[(j - root) mod 12]
+        const int src = (j - root + 12) % 12;
+        alt[j] = kKrumhansl[minor][src];
+        key[j] = kKrumhansl[minor][src] * W[minor][src];
+      }
+      const double den = np_sum12(key) + 1e-10;
+      for (int j = 0; j < 12; ++j) key[j] = key[j] / den;
+      // note_names holds sharps: of jazz's ['F', 'Bb', 'Eb', 'Ab'] only F ever matches (:307)
+      double fac = 1.0;
+      if (genre == OMEGA_TONAL_JAZZ && root == 5) fac = 1.1;
+      if (genre == OMEGA_TONAL_CLASSICAL && !minor && (root == 0 || root == 7 || root == 2 || root == 9 || root == 5)) fac = 1.05;
+      if (genre == OMEGA_TONAL_ROCK && (root == 4 || root == 9 || root == 2 || root == 7)) fac = 1.05;
+      t[kTnTabFac + k] = fac;
+    }
+  for (int j = 0; j < 12; ++j) t[kTnTabW + j] = W[0][j] + W[1][j];
+  return t;
+}
+
 }  // namespace omega_host

@@ -71,4 +71,12 @@ std::vector<int> fft_radices(int n);
 void savgol_cubic(int w, double* W);
 void np_leaves(int off, int n, int depth, std::vector<unsigned>& out);
 
+// ChromagramAnalyzer's genre settings (chromagram.py:37-68, :226-234; genre: omega_tonal_genre, `other` reads pop's
+// weights and tolerance as genre_profiles.get(..., pop) does): the blend factor, chromatic_tolerance, and the table
+// tonal.hip reads (params.hpp kTnTab*) -- per key 2 root + minor the rotated weighted profile / (its sum + 1e-10)
+// (:279-288), the key factors (:305-328), Mw + mw (:272), the plain rotated Krumhansl profiles (:403-404)
+double tonal_blend(int genre);
+double tonal_tolerance(int genre);
+std::vector<double> tonal_table(int genre);
+
 }  // namespace omega_host

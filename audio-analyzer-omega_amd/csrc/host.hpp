@@ -64,6 +64,7 @@ hipError_t launch_basszoom_frames(const BassZoomParams& p, hipStream_t s);
 hipError_t launch_basszoom_track(const BassZoomParams& p, hipStream_t s);
 hipError_t launch_waterfall(const WaterfallParams& p, hipStream_t s);
 hipError_t launch_waterfall_colors(const WaterfallColorParams& p, hipStream_t s);
+hipError_t launch_tonal(const TonalParams& p, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -194,6 +195,17 @@ struct RhythmState {
 struct WaterfallState {
   bool set = false;
   int n_bins = 0, first_bin = 0, n_cells = 0;
+  double* chain[2] = {};
+};
+
+// capi_tonal.cpp -- key, chord and mode scores (omega_tonal_configure / omega_tonal_features / omega_tonal_spectra):
+// the configured genre, the raw chroma rows omega_tonal_spectra keeps on the device between its two kernels, and
+// the two state blobs that chain a call's launches (the stream's state travels with the caller)
+struct TonalState {
+  bool set = false;
+  int genre = 0;
+  double* raw = nullptr;
+  int64_t raw_cap = 0;
   double* chain[2] = {};
 };
 
@@ -376,6 +388,7 @@ struct omega_ctx {
   BassZoomState basszoom;
   RhythmState rhythm;
   WaterfallState waterfall;
+  TonalState tonal;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables
@@ -561,6 +574,14 @@ SpectralParams spectral_params(omega_ctx* c);
 std::vector<int64_t> chunk_frames(int64_t n_frames);
 std::vector<MeterPrepParams> meter_chunks(const omega_ctx* c, const std::vector<ChunkSync>& chunks, const float* lufs,
                                           const float* tp, double* out);
+
+// capi_spectrum.cpp: omega_chroma's projection for (n_bins, df) from omega_ctx::chroma_mats, built on first use --
+// the [12, hi - lo] matrix and the bin range [lo, hi) it covers
+struct ChromaMat {
+  const double* mat;
+  int lo, hi;
+};
+int get_chroma_mat(omega_ctx* c, int n_bins, double df, ChromaMat* out);
 
 // ---- host-memory staging (inline: omega_process_frames calls these on every step) ----
 // Page-locked host buffer of at least `bytes` (grown on demand; hipHostMalloc).

@@ -721,6 +721,46 @@ struct WaterfallColorParams {
   unsigned char* rgb;
 };
 
+// ChromagramAnalyzer's key, chord and alternative-key scores and MusicTheory.analyze_mode for every root
+// (tonal.hip; omega4/panels/chromagram.py:215-339, :396-418, :670-812 and music_theory.py:175-200): G lanes per
+// frame, kTnThreads / G frames per workgroup
+constexpr int kTnThreads = 256;
+#ifndef OMEGA_TONAL_LANES           // (64, one wave per frame, builds the measured alternative)
+#define OMEGA_TONAL_LANES 16
+#endif
+constexpr int kTnLanes = OMEGA_TONAL_LANES;  // lanes per frame: 16 (sixteen frames per workgroup) or 64
+constexpr int kTnCols = 52;          // see include/omega.h for the columns
+constexpr int kTnKeys = 24, kTnTypes = 13, kTnCells = 12 * kTnTypes, kTnModes = 7;
+constexpr int kTnStateLen = 13;      // has-previous flag, the previous frame's rolled row
+enum TnFlag : int { kTnNonFinite = 1, kTnZeroSum = 2, kTnFlat = 4 };
+enum TnGenre : int { kTnPop = 0, kTnJazz, kTnClassical, kTnMetal, kTnRock, kTnOther, kTnGenres };
+// the per-genre table (design.hpp tonal_table): the 24 weighted normalised profiles (index 2 root + minor), the
+// key factors, Mw + mw, the 24 plain rotated profiles
+constexpr int kTnTabKey = 0, kTnTabFac = kTnTabKey + kTnKeys * 12, kTnTabW = kTnTabFac + kTnKeys,
+              kTnTabAlt = kTnTabW + 12, kTnTabLen = kTnTabAlt + kTnKeys * 12;
+// chord_types in dict order (chromagram.py:79-93; tonal.hip has the intervals): the per-genre tested sets as bit masks
+constexpr int kTnPower = 10;
+constexpr unsigned kTnTypesAll = 0x1FFF;
+constexpr unsigned kTnTypesMetal = 1u << 0 | 1u << 1 | 1u << 6 | 1u << 10 | 1u << 11 | 1u << 12;  // :680-681
+constexpr unsigned kTnTypesBasic = 0x3F;                                                          // :684-685
+struct TonalParams {
+  const double* raw;        // [n_frames, 12] chroma_kernel's rows
+  int64_t n_frames;
+  const int* roll;          // [n_frames] -11..11 or nullptr (0)
+  const int* first;         // [n_frames] or nullptr (0): the frame has no predecessor
+  int genre;                // TnGenre
+  double blend;             // 0.7 / 0.5 / 0.3
+  double tolerance;         // chromatic_tolerance
+  const double* tab;        // [kTnTabLen] the genre's table
+  const double* state_in;   // [kTnStateLen] or nullptr
+  double* state_out;        // [kTnStateLen] or nullptr
+  double* rows;             // [n_frames, kTnCols]
+  double* key_corr;         // [n_frames, 24] or nullptr
+  double* alt_corr;         // [n_frames, 24] or nullptr
+  double* chord;            // [n_frames, 2, 12, 13] or nullptr
+  double* mode;             // [n_frames, 12, 7] or nullptr
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

@@ -18,9 +18,11 @@ from .bass_zoom import BassZoomPanel
 from .beat_detection import BeatDetectionPanel, BeatDetector
 from .frequency_band_tracker import FrequencyBandTracker, FrequencyBandTrackerPanel
 from .spectrogram_waterfall import SpectrogramWaterfall, SpectrogramWaterfallPanel
+from .chromagram import ChromagramAnalyzer, ChromagramPanel
+from .music_theory import MusicTheory
 
 __all__ = [
-    "SpectrogramWaterfall", "SpectrogramWaterfallPanel",
+    "SpectrogramWaterfall", "SpectrogramWaterfallPanel", "ChromagramAnalyzer", "ChromagramPanel", "MusicTheory",
     "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector", "PhaseCorrelation",
     "RoomModeAnalyzer", "RoomModeConfig", "VoiceDetectionPanel", "TransientDetectionPanel", "BassZoomPanel",
     "BeatDetector", "BeatDetectionPanel", "FrequencyBandTracker", "FrequencyBandTrackerPanel",

@@ -97,6 +97,10 @@ class WaterfallConfig(C.Structure):
     _fields_ = [("n_bins", C.c_int32), ("first_bin", C.c_int32), ("n_cells", C.c_int32)]
 
 
+class TonalConfig(C.Structure):
+    _fields_ = [("genre", C.c_int32)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -193,6 +197,12 @@ EXPORTS = {
                                        C.c_int32] + [C.c_void_p] * 5 + [C.c_int]),
     "omega_waterfall_colors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                          C.c_void_p, C.c_int]),
+    "omega_tonal_config_default": (None, [C.POINTER(TonalConfig)]),
+    "omega_tonal_configure": (C.c_int, [C.c_void_p, C.POINTER(TonalConfig)]),
+    "omega_tonal_state_size": (C.c_int64, []),
+    "omega_tonal_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 9 + [C.c_int]),
+    "omega_tonal_spectra": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double] + [C.c_void_p] * 9
+                            + [C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -46,6 +46,9 @@
  *   omega_waterfall_*      SpectrogramWaterfall.update, _spectrum_to_color omega4/panels/spectrogram_waterfall.py:56-121,
  *                          :142-205 and SpectrogramWaterfallPanel.update  :295-305 (omega_waterfall_config_default,
  *                          _mapping, _configure, _state_size, _rows, _colors)
+ *   omega_tonal_*          ChromagramAnalyzer.detect_key, get_alternative_keys, detect_chord
+ *                          omega4/panels/chromagram.py:215-339, :396-418, :670-812 and MusicTheory.analyze_mode
+ *                          omega4/panels/music_theory.py:175-200 (§8(f) row 13)
  *
  * Conventions:
  *   - every function returns 0 on success and a negative omega_status on error; the message is
@@ -935,6 +938,64 @@ int omega_waterfall_rows(omega_ctx* ctx, const void* spectra, int64_t spec_strid
                          double* stats, void* rows, uint8_t* rgb, int mem);
 int omega_waterfall_colors(omega_ctx* ctx, const void* intensity, int64_t row_stride, int32_t f64, int64_t n_rows,
                            int32_t n_cells, int32_t scheme, uint8_t* rgb, int mem);
+
+/* ChromagramAnalyzer.detect_key / get_alternative_keys / detect_chord with the temporal blend in front of them, and
+ * MusicTheory.analyze_mode for every root (omega4/panels/chromagram.py:215-339, :396-418, :670-812;
+ * omega4/panels/music_theory.py:175-200) for consecutive frames of one stream, in float64. The histories, the names
+ * and every rule that reads them (the flat-chroma chord fallback, the metal riff pattern, anti-stick's repeat count,
+ * the history-append rule) stay with the caller (omega_gpu.ChromagramAnalyzer / ChromagramPanel). The context keeps
+ * only the configuration; the caller carries the stream's state, omega_tonal_state_size() float64 values (a
+ * has-previous flag and the previous frame's rolled raw row), from state_out of one call to state_in of the next.
+ * state_in NULL: no predecessor. state_out NULL: not wanted. Both live where `mem` says and may be the same buffer.
+ * One call on F frames equals F one-frame calls chained through the blob, bit for bit; n_frames 0 passes the state
+ * through. The entry points are additive to ABI 5.
+ * omega_tonal_configure fixes the genre (omega_tonal_genre; any other value returns OMEGA_EINVAL and leaves the
+ * configuration as it was) and may be repeated; it needs no device. `other` is what the reference does for a genre
+ * name it does not know: pop's weights and tolerance, the pop / classical chord types, threshold 0.03, blend 0.3,
+ * no key factor and no chord bonus. The blend factor is 0.7 for metal and rock, 0.5 for jazz, else 0.3.
+ * omega_tonal_features: raw_chroma [n_frames, 12] float64 as omega_chroma writes it (smoothed, normalised, not yet
+ * blended). roll [n_frames] int32 or NULL (0): the frame's tuning offset in semitones, -11..11, applied as
+ * np.roll(row, roll); a value outside returns OMEGA_EINVAL before anything is launched (for OMEGA_MEM_DEVICE the
+ * array is read back first, which waits for the context's stream). first [n_frames] int32 or NULL (0): non-zero
+ * marks a frame without predecessor (it stays unblended, whatever the carry holds). Per frame: blended =
+ * prev * (1 - a) + cur * a of the rolled rows, then
+ *   rows [n_frames, OMEGA_TONAL_COLS] float64:
+ *     0..11  the blended chroma
+ *     12     flags: bit 0 a non-finite value (the frame is scored as the all-zero row), bit 1 np.sum == 0,
+ *            bit 2 np.var < 0.001
+ *     13     np.var of the blended chroma
+ *     14, 15 the key: index 2 root + (1 for minor) and its adjusted correlation (the first maximum, :331)
+ *     16..18, 19..21  the three best alternative keys by a stable descending sort (:417): indices, correlations
+ *     22, 23 the chord: cell 13 root + type in chord_types order, -1 for N/A, and its score (:754)
+ *     24..27 anti-stick (:781-818; metal and rock only, else -1 / 0): first index, first score, second index,
+ *            second score of a stable descending sort of the second matrix
+ *     28..39, 40..51  analyze_mode for root 0..11: the mode's index in MusicTheory.MODES order, and its score
+ *   key_corr [n_frames, 24], alt_corr [n_frames, 24] (index 2 root + minor), chord [n_frames, 2, 12, 13] (matrix 0
+ *   detect_chord's scores, matrix 1 the anti-stick variant; NaN where a cell is not tested), mode [n_frames, 12, 7]:
+ *   the scores behind the decisions; each may be NULL.
+ * Correlations and chord scores agree with numpy's to 1e-12 absolute.
+ * omega_tonal_spectra: the same from magnitude spectra [n_frames, n_bins] float32, contiguous, with omega_chroma's
+ * limits (n_bins >= 3, df > 0): omega_chroma's kernel writes the raw rows into context scratch and the tonal kernel
+ * runs behind it on the context's stream; nothing returns to the host in between. */
+#define OMEGA_TONAL_COLS 52
+typedef enum {
+  OMEGA_TONAL_POP = 0, OMEGA_TONAL_JAZZ = 1, OMEGA_TONAL_CLASSICAL = 2, OMEGA_TONAL_METAL = 3, OMEGA_TONAL_ROCK = 4,
+  OMEGA_TONAL_OTHER = 5
+} omega_tonal_genre;
+typedef struct {
+  int32_t genre; /* omega_tonal_genre */
+} omega_tonal_config;
+/* pop. */
+void omega_tonal_config_default(omega_tonal_config* cfg);
+int omega_tonal_configure(omega_ctx* ctx, const omega_tonal_config* cfg);
+/* 13; no context, no device. */
+int64_t omega_tonal_state_size(void);
+int omega_tonal_features(omega_ctx* ctx, const double* raw_chroma, int64_t n_frames, const int32_t* roll,
+                         const int32_t* first, const double* state_in, double* state_out, double* rows,
+                         double* key_corr, double* alt_corr, double* chord, double* mode, int mem);
+int omega_tonal_spectra(omega_ctx* ctx, const float* spectra, int64_t n_frames, int32_t n_bins, double df,
+                        const int32_t* roll, const int32_t* first, const double* state_in, double* state_out,
+                        double* rows, double* key_corr, double* alt_corr, double* chord, double* mode, int mem);
 
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Run one stage of the cfg2 hot path in isolation (for rocprofv3 counter passes and A/B timing).
 
-  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre,room,voice,waterfall} [--reps N]
+  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre,room,voice,waterfall,tonal} [--reps N]
 
 spectra-bands / spectra-chroma / spectra-mag: the cfg3 kernel with one output set only (where its LDS
 bank conflicts and time come from); spectra-rot: bench.py's cfg3 call, rotating over 4 distinct input
@@ -12,6 +12,8 @@ voice: omega_voice_features over 512 resident frames at the app's shape (K 1025,
 golden's `app` frames (tests/golden/voice.npz) repeated.
 waterfall: omega_waterfall_rows over 4096 resident frames (1025 bins, 853 cells; float32 and float64, with and without
 the RGB output) and omega_waterfall_colors over a 200 x 853 history; with --lib, another build of the same ABI.
+tonal: omega_tonal_features over 4096 resident chroma rows and omega_tonal_spectra over 4096 resident spectra of 4097
+bins, rows only and with the four detail matrices; with --lib, a build with another OMEGA_TONAL_LANES.
 """
 import argparse
 import os
@@ -161,6 +163,60 @@ def waterfall(reps):
     print("waterfall stats row 0:", stats[0].cpu().numpy())
 
 
+def tonal(reps):
+    """The two tonal entry points on resident inputs at 4096 frames, K = 4097 (metal: both chord matrices are live;
+    the features call once more in pop).
+    Three passes of `reps` calls each between one event pair; the median pass, per call."""
+    import ctypes as C
+    from omega_gpu import ChromagramAnalyzer
+    from omega_gpu import _lib as L
+    lib = L.lib()
+    rng = np.random.default_rng(14)
+    F, K = 4096, 4097
+    an = ChromagramAnalyzer(48000)
+    eng = an._eng
+    eng._check(lib.omega_tonal_configure(eng._ctx, C.byref(L.TonalConfig(3))))
+    spec = torch.from_numpy(np.abs(rng.standard_normal((F, K))).astype(np.float32) ** 4).cuda()
+    raw = torch.empty(F, 12, dtype=torch.float64, device="cuda")
+    eng._bind_stream(spec)
+    eng._check(lib.omega_chroma(eng._ctx, spec.data_ptr(), F, K, 24000.0 / (K - 1), raw.data_ptr(), L.MEM_DEVICE))
+    rows = torch.empty(F, 52, dtype=torch.float64, device="cuda")
+    det = [torch.empty(F, n, dtype=torch.float64, device="cuda") for n in (24, 24, 312, 84)]
+    state = torch.empty(13, dtype=torch.float64, device="cuda")
+
+    def timed(label, call):
+        for _ in range(5):
+            call()
+        torch.cuda.synchronize()
+        passes = []
+        for _ in range(3):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(reps):
+                call()
+            e.record()
+            e.synchronize()
+            passes.append(s.elapsed_time(e) * 1e3 / reps)
+        med = float(np.median(passes))
+        print(f"tonal {label}: median {med:.1f} us per call of {F} frames (passes {', '.join(f'{v:.1f}' for v in passes)}); "
+              f"{med / F * 1e3:.1f} ns per frame")
+
+    for name, d in (("rows only", [None] * 4), ("with details", [t.data_ptr() for t in det])):
+        timed(f"features, {name}", lambda: eng._check(lib.omega_tonal_features(
+            eng._ctx, raw.data_ptr(), F, None, None, None, state.data_ptr(), rows.data_ptr(), *d, L.MEM_DEVICE)))
+        timed(f"spectra K = {K}, {name}", lambda: eng._check(lib.omega_tonal_spectra(
+            eng._ctx, spec.data_ptr(), F, K, 24000.0 / (K - 1), None, None, None, state.data_ptr(), rows.data_ptr(), *d,
+            L.MEM_DEVICE)))
+    timed(f"omega_chroma K = {K} alone", lambda: eng._check(lib.omega_chroma(
+        eng._ctx, spec.data_ptr(), F, K, 24000.0 / (K - 1), raw.data_ptr(), L.MEM_DEVICE)))
+    # pop: the second chord matrix is not computed (stored as NaN), six chord types are scored
+    eng._check(lib.omega_tonal_configure(eng._ctx, C.byref(L.TonalConfig(0))))
+    timed("features, rows only, pop", lambda: eng._check(lib.omega_tonal_features(
+        eng._ctx, raw.data_ptr(), F, None, None, None, state.data_ptr(), rows.data_ptr(), None, None, None, None,
+        L.MEM_DEVICE)))
+    print("tonal row 0:", rows[0, 12:28].cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("stage")
@@ -178,6 +234,8 @@ def main():
         return voice(a.reps)
     if a.stage == "waterfall":
         return waterfall(a.reps)
+    if a.stage == "tonal":
+        return tonal(a.reps)
     import bench
     from omega_gpu import NORTHSTAR_RESOLUTIONS, Engine
     from omega_gpu import _lib as L
