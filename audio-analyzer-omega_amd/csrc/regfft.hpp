@@ -27,18 +27,25 @@
 
 namespace omega {
 
-// cos / sin(2 pi r / 128), r < 16: the true-peak rotation e^{2 pi i k / 4M} of element
-// k = t + NTH r relative to the thread's base k = t (NTH / 4M = 1/128 for M = 32 NTH)
-__device__ constexpr float kCos128[16] = {
-    1.000000000e+00f, 9.987954562e-01f, 9.951847267e-01f, 9.891765100e-01f, 9.807852804e-01f,
-    9.700312532e-01f, 9.569403357e-01f, 9.415440652e-01f, 9.238795325e-01f, 9.039892931e-01f,
-    8.819212643e-01f, 8.577286100e-01f, 8.314696123e-01f, 8.032075315e-01f, 7.730104534e-01f,
-    7.409511254e-01f};
-__device__ constexpr float kSin128[16] = {
-    0.000000000e+00f, 4.906767433e-02f, 9.801714033e-02f, 1.467304745e-01f, 1.950903220e-01f,
-    2.429801799e-01f, 2.902846773e-01f, 3.368898534e-01f, 3.826834324e-01f, 4.275550934e-01f,
-    4.713967368e-01f, 5.141027442e-01f, 5.555702330e-01f, 5.956993045e-01f, 6.343932842e-01f,
-    6.715589548e-01f};
+// cos(pi j / 64), j <= 32 (sin(pi j / 64) = kCos64[32 - j]): the true peak's compile-time rotations
+// e^{i pi j / 64} -- phase p turns element k = t + NTH r by e^{2 pi i k p / 4M} e^{-i pi p / 8}, which
+// relative to the thread's base k = t is j = p (r - 8) (NTH / 4M = 1/128 for M = 32 NTH) -- and the
+// phase weights cos / sin(pi p / 8); in double, so that a product of two rounds to float once
+__device__ constexpr double kCos64[33] = {
+    1.00000000000000000e+00, 9.98795456205172405e-01, 9.95184726672196929e-01, 9.89176509964781014e-01,
+    9.80785280403230431e-01, 9.70031253194543974e-01, 9.56940335732208824e-01, 9.41544065183020806e-01,
+    9.23879532511286738e-01, 9.03989293123443338e-01, 8.81921264348355050e-01, 8.57728610000272118e-01,
+    8.31469612302545236e-01, 8.03207531480644943e-01, 7.73010453362736993e-01, 7.40951125354959106e-01,
+    7.07106781186547573e-01, 6.71558954847018330e-01, 6.34393284163645488e-01, 5.95699304492433468e-01,
+    5.55570233019602289e-01, 5.14102744193221661e-01, 4.71396736825997809e-01, 4.27555093430282196e-01,
+    3.82683432365089837e-01, 3.36889853392220051e-01, 2.90284677254462331e-01, 2.42980179903263982e-01,
+    1.95090322016128331e-01, 1.46730474455361748e-01, 9.80171403295607702e-02, 4.90676743274181260e-02,
+    0.00000000000000000e+00};
+// e^{i pi J / 64}, |J| <= 32
+template <int J>
+constexpr double rot64_re() { return kCos64[J < 0 ? -J : J]; }
+template <int J>
+constexpr double rot64_im() { return J < 0 ? -kCos64[32 + J] : kCos64[32 - J]; }
 
 // This wave's LDS stores are complete before its next LDS reads (a wave-local exchange: no s_barrier)
 __device__ __forceinline__ void wave_lds_sync() {
@@ -197,6 +204,16 @@ struct RegFFT {
     });
   }
 
+  // v[k] *= c w^k, k = 0..15: a factor c common to the thread's pass-1 inputs commutes with the DFT16
+  // and rides on the chain's seed (one multiplication more than twiddle(), instead of 16 before it)
+  static __device__ __forceinline__ void twiddle_seeded(float2 (&v)[16], float2 c, float2 w) {
+    float2 wk = c;
+    static_for<0, 16>([&](auto k) {
+      v[k] = cmul(v[k], wk);
+      if constexpr (k + 1 < 16) wk = cmul(wk, w);
+    });
+  }
+
   // 16-point DFT in registers, natural order out
   static __device__ __forceinline__ void dft16(float2 (&v)[16]) { dft16_fma(v); }
 
@@ -225,13 +242,17 @@ struct RegFFT {
   }
   // run() with the pass-1 input column t1 (v[r] = x[t1 + NTH r], w1 = W_K^t1) decoupled from the
   // thread's pass-2/3 role t (w2 = W_K^{16 (t mod L)}): any bijection tid -> t1 (the true peak pairs
-  // mirror columns t1, NTH - t1 inside one wave).
-  template <bool SYNC = false, bool LT2 = false>
+  // mirror columns t1, NTH - t1 inside one wave). SEED: the transform of c1 x, c1 the thread's own
+  // factor, applied with pass 1's twiddles (twiddle_seeded).
+  template <bool SYNC = false, bool LT2 = false, bool SEED = false>
   static __device__ __forceinline__ void run2(float2 (&v)[16], float2* buf, int t1, int t, float2 w1, float2 w2,
-                                              const float2* t2 = nullptr) {
+                                              const float2* t2 = nullptr, float2 c1 = make_float2(1.f, 0.f)) {
     // pass 1
     dft16(v);
-    twiddle(v, w1);
+    if constexpr (SEED)
+      twiddle_seeded(v, c1, w1);
+    else
+      twiddle(v, w1);
     if constexpr (SYNC) __syncthreads();
     {
       float2* b = buf + t1;

@@ -4,16 +4,17 @@
 //   A8  professional_meters.py:283-299  4x true peak (polyphase form, see spectral.hip)
 //
 // True peak of one frame of M = 2K samples, thread t owning the spectrum bins S_t = {t + NTH r}:
-//   rfft: z[n] = x[2n] + i x[2n+1], Z = FFT_K(z) (input straight from HBM into registers), Z written
-//     in natural order, then X_k = E + W_M^k O from (Z_k, Z_{K-k}) for k in S_t (X_0 and the Nyquist
-//     bin X_K on thread 0).
-//   phase p = 1..3: Y_k = X_k rho_k^p (running product, rho_k = e^{2 pi i k / 4M}); the mirror Y_{K-k}
-//     from the lane that owns column NTH - t (tp_column: lanes l and l ^ 63 of a wave hold mirror
-//     columns, ds_bpermute, no LDS exchange); the packed inverse spectrum
-//       Z'_k = conj(Y' + alpha_k (Y_k - Y')),  Y' = conj(Y_{K-k}) (Nyquist share X_K cos(pi p/4) at
-//       k = 0), alpha_k = (1 + i e^{2 pi i k / M}) / 2
-//     is the first pass's input, in registers; the forward FFT of Z' is conj(K * y_p) packed, reduced
-//     to max |.| from the last pass's registers.
+//   packed forward transform: z[n] = x[2n] + i x[2n+1], F = FFT_K(z) (input straight from HBM into
+//     registers), F written in natural order; from (F_k, F_{K-k}), k in S_t, the phase-independent
+//     S_k = Im(W_M^k) F_k + Re(W_M^k) i conj(F_{K-k}) -- the real spectrum X_k is never formed.
+//   phase p = 1..3: the packed inverse spectrum of Y_k = X_k e^{2 pi i k p / 4M} (Nyquist share
+//     X_K cos(pi p/4)) is
+//       Z'_k = conj(e^{-i pi p / 8} e^{2 pi i k p / 4M} (cos(pi p / 8) F_k + i sin(pi p / 8) S_k)),
+//       Z'_0 = conj(cos^2(pi p / 8) F_0 + sin^2(pi p / 8) S_0)
+//     (derivation and edge bins: tools/model/tp_pack_model.py), the first pass's input, in registers:
+//     two real weights and one compile-time rotation per bin, the thread's own e^{2 pi i t p / 4M} on
+//     pass 1's twiddle seed, no mirror fetch per phase; the forward FFT of Z' is conj(K * y_p) packed,
+//     reduced to max |.| from the last pass's registers.
 // Per frame: 4 transforms, 9 LDS exchanges of 64 KiB (the old 1024-thread radix-8 kernel: 19).
 #include <cstdlib>
 
@@ -44,8 +45,8 @@ __device__ __forceinline__ float2* t2_table(char* smem) { return reinterpret_cas
 
 // Column map of the true peak: thread tid = 64 w + l owns spectrum column t = 32 w + l (l < 32), and
 // lane l ^ 63 the mirror column NTH - t (column NTH / 2 for t = 0); columns 0 and NTH / 2 mirror
-// themselves -- each phase's mirror spectrum comes by ds_bpermute inside the wave instead of an LDS
-// exchange with two barriers
+// themselves. (The map dates from the per-phase mirror fetch by ds_bpermute inside the wave; the phases
+// need no mirror now, the map stays because the exchanges' bank patterns were checked for it.)
 template <int NTH>
 __device__ __forceinline__ int tp_column(int tid) {
   const int w = tid >> 6, l = tid & 63;
@@ -124,95 +125,74 @@ __device__ __forceinline__ void truepeak_rf_body(const SpectralParams& p, int64_
   OMEGA_STAMP(1);
   FFT::template run2<false, true>(v, buf, t, tid, w1, w2, t2);
   OMEGA_STAMP(2);
-  // natural-order spectrum -> X_k on k in S_t
+  // natural-order spectrum -> F_k and its mirror on k in S_t
   __syncthreads();
   FFT::store_spectrum(v, buf, tid);
   __syncthreads();
   OMEGA_STAMP(3);
-  float xn = 0.f;  // X_K (thread 0)
+  // F_k and the phase-independent S_k = Im(W_M^k) F_k + Re(W_M^k) i conj(F_{K-k}) on k in S_t, held for
+  // the three phases (iS = i S_k). Thread 0: F_K is F_0, so S_0 = Im F_0 + i Re F_0.
+  float2 F[16], iS[16];
   {
     const float2* bo = buf + FFT::s3(t);
     const float2* bm = buf + FFT::s3m(t);
     static_for<0, 16>([&](auto r) {
       const float2 a = bo[FFT::o3(r)];
       float2 b = bm[FFT::o3(15 - r)];
-      if constexpr (K == 8192 && r == 8) {
-        if (t == 0) b = a;  // K/2 is its own mirror
+      if constexpr (r == 0 || (K == 8192 && r == 8)) {
+        if (t == 0) b = a;  // bins 0 and K/2 mirror themselves
       }
-      float2 xk, xkk;
-      untangle(a, b, twc<r, 32>(wm), xk, xkk);  // W_M^k = W_M^t e^{-2 pi i r / 32}
-      if constexpr (r == 0) {
-        if (t == 0) {
-          xn = a.x - a.y;
-          xk = make_float2(a.x + a.y, 0.f);
-        }
-      }
-      v[r] = xk;
+      const float2 wk = twc<r, 32>(wm);  // W_M^k = W_M^t e^{-2 pi i r / 32}
+      F[r] = a;
+      iS[r] = make_float2(-fmaf(wk.y, a.y, wk.x * b.x), fmaf(wk.y, a.x, wk.x * b.y));
     });
   }
-  float2 y[16];
-  static_for<0, 16>([&](auto r) { y[r] = v[r]; });
-  // i e^{2 pi i t / M}: 2 alpha_k = (1, 0) + (that) e^{2 pi i r / 32} -- the phases' transforms take
-  // 2 Z'_k (one multiply fewer per bin), their maxima are halved at the end
-  const float2 hz = make_float2(wm.y, wm.x);
   float fmx = 0.f;
-  // byte address of the lane holding the mirror column (itself for columns 0 and NTH / 2)
-  const int lane = tid & 63;
-  const int mir_addr = 4 * ((t == 0 || t == NTH / 2) ? lane : lane ^ 63);
   OMEGA_STAMP(4);
-#pragma unroll 1
-  for (int P = 1; P <= 3; ++P) {
-    // opaque per-iteration copies: keep the inlined FFT's address arithmetic and twiddle powers
-    // inside the loop instead of hoisted and pinned in VGPRs across it
-    int tl = t, tidl = tid;
-    float2 w1l = w1, w2l = w2, rhol = rho, hzl = hz;
-    asm volatile("" : "+v"(tl), "+v"(tidl), "+v"(w1l.x), "+v"(w1l.y), "+v"(w2l.x), "+v"(w2l.y));
-    asm volatile("" : "+v"(rhol.x), "+v"(rhol.y), "+v"(hzl.x), "+v"(hzl.y));
-    static_for<0, 16>([&](auto r) {
-      const float2 rk = cmul(rhol, make_float2(kCos128[r], kSin128[r]));
-      y[r] = cmul(y[r], rk);
-    });
-    if (!((p.tp_phases >> P) & 1)) continue;  // phase not requested (oversampling 2 or 1)
-    OMEGA_STAMP(1 + 4 * P);
-    const float cp = P == 1 ? 7.071067812e-01f : (P == 2 ? 0.f : -7.071067812e-01f);
-    OMEGA_STAMP(2 + 4 * P);
-    static_for<0, 16>([&](auto r) {
-      // Y_{K-k}, k = t + NTH r: register 15 - r of the mirror lane (t >= 1); column 0 holds its own
-      // mirrors in register 16 - r (r >= 1)
-      const float2 m = y[15 - r];
-      float2 yp = make_float2(__int_as_float(__builtin_amdgcn_ds_bpermute(mir_addr, __float_as_int(m.x))),
-                              -__int_as_float(__builtin_amdgcn_ds_bpermute(mir_addr, __float_as_int(m.y))));
-      if constexpr (r == 0) {
-        if (tl == 0) yp = make_float2(xn * cp, 0.f);
-      } else {
-        if (tl == 0) yp = cconj(y[16 - r]);
-      }
-      // 2 Z'_k = conj(S + g D), S = Y_k + Y', D = Y_k - Y', g = (i e_t) e^{2 pi i r / 32}
-      const float2 g = twc<-r, 32>(hzl);
-      const float2 S = cadd(y[r], yp), D = csub(y[r], yp);
-      v[r] = make_float2(fmaf(g.x, D.x, fmaf(-g.y, D.y, S.x)), fmaf(-g.x, D.y, fmaf(-g.y, D.x, -S.y)));
-    });
-    OMEGA_STAMP(3 + 4 * P);
-    FFT::template run2<true, true>(v, buf, tl, tidl, w1l, w2l, t2);
-    // max |.| by v_max3_f32 with abs modifiers, one instruction per register: the pass-3 outputs come
-    // from inline asm (RegFFT lane_pair_fmac), so fmaxf would first canonicalize every one of them
-    max3_abs16(fmx, v);
-#if defined(OMEGA_EXP_STALL)  // energy-vs-stall experiment, never in the product:
-    // idle issue cycles per phase and wave, no VALU
-    asm volatile("s_sleep %0" ::"i"(OMEGA_EXP_STALL));
-#endif
-#if defined(OMEGA_EXP_VALU)  // the converse: 4 x OMEGA_EXP_VALU FMAs on dead registers, four independent chains
-    {
-      float d0 = fmx, d1 = mx, d2 = fmx + 1.f, d3 = mx + 1.f;
-      asm volatile(".rept %4\n v_fma_f32 %0, %0, %5, %6\n v_fma_f32 %1, %1, %5, %6\n"
-                   " v_fma_f32 %2, %2, %5, %6\n v_fma_f32 %3, %3, %5, %6\n .endr"
-                   : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3)
-                   : "i"(OMEGA_EXP_VALU), "v"(0.5f), "v"(0.25f));
+  // phase P: Z'_k = conj(e^{-i pi P / 8} r^k (cos(pi P / 8) F_k + sin(pi P / 8) iS_k)), r = e^{2 pi i P / 4M}.
+  // r^k = rho^P e^{2 pi i P r / 128} on k = t + NTH r: the part that depends on r joins the e^{-i pi P / 8}
+  // in a compile-time rotation, the thread's own rho^P multiplies pass 1's twiddle seed.
+  float2 rhoP = rho;
+  static_for<1, 4>([&](auto P) {
+    if constexpr (P > 1) rhoP = cmul(rhoP, rho);
+    if ((p.tp_phases >> P) & 1) {  // (else: phase not requested, oversampling 2 or 1)
+      // opaque per-phase copies: keep the inlined FFT's address arithmetic and twiddle powers inside
+      // the phase instead of shared between the three and pinned in VGPRs across them
+      int tl = t, tidl = tid;
+      float2 w1l = w1, w2l = w2;
+      asm volatile("" : "+v"(tl), "+v"(tidl), "+v"(w1l.x), "+v"(w1l.y), "+v"(w2l.x), "+v"(w2l.y));
+      OMEGA_STAMP(1 + 4 * P);
+      OMEGA_STAMP(2 + 4 * P);
+      constexpr double cp = kCos64[8 * P], sp = kCos64[32 - 8 * P];
+      static_for<0, 16>([&](auto r) {
+        // conj(A F + B iS), A = cos(pi P / 8) R, B = sin(pi P / 8) R, R the rotation: each product
+        // rounded to float once (two weights rounded on their own bias every bin of the phase one way:
+        // -3e-7 dB on a band-limited pulse in a float32 restatement of the pack)
+        constexpr int J = P * (r - 8);
+        constexpr float ax = float(cp * rot64_re<J>()), ay = float(cp * rot64_im<J>());
+        constexpr float bx = float(sp * rot64_re<J>()), by = float(sp * rot64_im<J>());
+        if constexpr (J == 0) {
+          v[r] = make_float2(fmaf(ax, F[r].x, bx * iS[r].x), -fmaf(ax, F[r].y, bx * iS[r].y));
+        } else if constexpr (P == 2) {  // A = B
+          const float2 H = cadd(F[r], iS[r]);
+          v[r] = make_float2(fmaf(ax, H.x, -ay * H.y), -fmaf(ax, H.y, ay * H.x));
+        } else {
+          v[r] = make_float2(fmaf(ax, F[r].x, fmaf(-ay, F[r].y, fmaf(bx, iS[r].x, -by * iS[r].y))),
+                             -fmaf(ax, F[r].y, fmaf(ay, F[r].x, fmaf(bx, iS[r].y, by * iS[r].x))));
+        }
+      });
+      // k = 0: X_0 mirrors itself and the Nyquist bin weighs cos(pi P / 4): conj(Z'_0) = cos^2 F_0 + sin^2 S_0
+      constexpr float c2 = float(cp * cp), s2 = float(sp * sp);
+      if (tl == 0) v[0] = make_float2(fmaf(c2, F[0].x, s2 * iS[0].y), fmaf(s2, iS[0].x, -c2 * F[0].y));
+      OMEGA_STAMP(3 + 4 * P);
+      FFT::template run2<true, true, true>(v, buf, tl, tidl, w1l, w2l, t2, cconj(rhoP));
+      // max |.| by v_max3_f32 with abs modifiers, one instruction per register: the pass-3 outputs come
+      // from inline asm (RegFFT lane_pair_fmac), so fmaxf would first canonicalize every one of them
+      max3_abs16(fmx, v);
+      OMEGA_STAMP(4 + 4 * P);
     }
-#endif
-    OMEGA_STAMP(4 + 4 * P);
-  }
-  const float peak = block_max<NTH>(fmaxf(mx, fmx * (0.5f / K)), red, tid);
+  });
+  const float peak = block_max<NTH>(fmaxf(mx, fmx * (1.0f / K)), red, tid);
   if (tid == 0) {
     const float db = tp_db(peak);
     if (p.tp_done) {  // write-through, drained, then counted in (see SpectralParams::tp_done)
