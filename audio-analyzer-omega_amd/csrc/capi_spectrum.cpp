@@ -3,47 +3,6 @@
 
 #include "host.hpp"
 
-namespace {
-
-// The window of make_window as the register-FFT bodies' generator (regfft.hpp WinGen): with
-// phi = pi n / (M - 1), n = 1 - M + 2i, cos(phi) = -C_i and cos(2 phi) = 2 C_i^2 - 1, C_i = cos(2 pi i / (M - 1)),
-// so a0 + a1 cos(phi) + a2 cos(2 phi) = (a0 - a2) + C_i (-a1 + 2 a2 C_i); thread t of NTH = M / 32 takes the
-// points 2 (t + NTH q) + e
-int build_wingen(omega_ctx* c, int m, int kind, float4** out) {
-  if (m < 1024 || m % 32) return fail(c, OMEGA_EINVAL, "window generator: %d points", m);
-  double a0 = 1.0, a1 = 0.0, a2 = 0.0;
-  switch (kind) {
-    case OMEGA_WIN_BLACKMAN: a0 = 0.42; a1 = 0.5; a2 = 0.08; break;
-    case OMEGA_WIN_HANN: a0 = 0.5; a1 = 0.5; break;
-    case OMEGA_WIN_HAMMING: a0 = 0.54; a1 = 0.46; break;
-    default: break;
-  }
-  const int nth = m / 32;
-  const double th = 2.0 * kPi / (m - 1);
-  std::vector<float4> g(9 + nth);
-  g[0] = make_float4((float)(a0 - a2), (float)(-a1), (float)(2.0 * a2), 0.f);
-  for (int q = 0; q < 16; ++q) {
-    const double b = th * (2.0 * nth * q);
-    float4& e = g[1 + q / 2];
-    if (q & 1) {
-      e.z = (float)std::cos(b);
-      e.w = (float)std::sin(b);
-    } else {
-      e.x = (float)std::cos(b);
-      e.y = (float)std::sin(b);
-    }
-  }
-  for (int t = 0; t < nth; ++t)
-    g[9 + t] = make_float4((float)std::cos(th * 2 * t), (float)std::sin(th * 2 * t), (float)std::cos(th * (2 * t + 1)),
-                           (float)std::sin(th * (2 * t + 1)));
-  return upload(c, out, g);
-}
-int get_wingen(omega_ctx* c, int m, int kind, float4** out) {
-  return cached(c->wgens, std::make_pair(m, kind), out, [&](float4** d) { return build_wingen(c, m, kind, d); });
-}
-
-}  // namespace
-
 extern "C" {
 
 int omega_rfft(omega_ctx* c, const float* x, int64_t n, int32_t m, int32_t window, float* mag, float* cplx, int mem) try {
@@ -177,9 +136,6 @@ int omega_spectra(omega_ctx* c, const float* x, int64_t n, int32_t m, int32_t wi
   p.n = n;
   p.stride = m;
   p.win = win;
-  float4* wgen = nullptr;
-  if (m == 8192 && (e = get_wingen(c, m, window, &wgen))) return e;
-  p.wgen = wgen;
   p.mag_out = dm;
   if (bands_out) {
     p.n_out = bands->n_out;

@@ -211,24 +211,43 @@ __device__ __forceinline__ int swz(int i) {
 // for its one butterfly j = tid. Loaded once, up front, with the frame's first global loads (one
 // memory latency for the whole transform instead of one per pass), and reused by every transform a
 // kernel runs with the same plan.
-template <int NP>
+// h: the base's 8th power w^8 = tw[8 (j mod NS) K/(NS R)] of the twiddled radix-16 passes (bit I of H16), read
+// from the table like w: the multiply chain of fft_pass restarts from it.
+template <int NP, unsigned H16 = 0>
 struct TwReg {
   float2 w[NP > 0 ? NP : 1];
+  float2 h[NP > 0 ? NP : 1];
   // Make the values opaque to the optimiser: inside a loop that runs several transforms this stops
   // LICM from hoisting every pass's twiddle powers (w^2 .. w^(R-1)) and pinning them in VGPRs.
   __device__ __forceinline__ void launder() {
-    static_for<0, (NP > 0 ? NP : 1)>([&](auto i) { asm volatile("" : "+v"(w[i].x), "+v"(w[i].y)); });
+    static_for<0, (NP > 0 ? NP : 1)>([&](auto i) {
+      asm volatile("" : "+v"(w[i].x), "+v"(w[i].y));
+      if constexpr ((H16 >> i) & 1) asm volatile("" : "+v"(h[i].x), "+v"(h[i].y));
+    });
   }
 };
+
+// bit I set: pass I of the plan Rs... is a radix-16 pass with twiddles (not the first pass)
+template <int... Rs>
+constexpr unsigned radix16_passes() {
+  constexpr int r[] = {Rs...};
+  unsigned m = 0;
+  for (int i = 1; i < (int)sizeof...(Rs); ++i)
+    if (r[i] == 16) m |= 1u << i;
+  return m;
+}
 
 // One Stockham pass over K points with NTH threads: butterfly j in [0, K/R) reads logical elements
 // j + r*K/R (r < R) through `load`, multiplies element r by w^(r*k) with k = j mod NS and
 // w = exp(-2 pi i / (NS*R)), DFTs, and hands output m to `store` at logical index
 // (j/NS)*NS*R + k + m*NS. w1: the preloaded base w^k of this thread's butterfly (passes with NS > 1
-// have one butterfly per thread); its powers are formed by a multiply chain. SYNC_MID: loads and
+// have one butterfly per thread); its powers are formed by a multiply chain, which a radix-16 pass restarts
+// at w8 = w^8 from the table: the r-th power of a chain carries r - 1 roundings and r times the rounding of
+// the table's w1, which put a pure phase ramp (an impulse at the end of a frame) 10-15 ulps off per bin and
+// past eps32 log2(2N) at 1024 points (tests/test_pow2_rfft_bins.py). SYNC_MID: loads and
 // stores hit the same LDS buffer in place, so a barrier separates all reads from all writes.
 template <int K, int R, int NS, int NTH, bool SYNC_MID, class Load, class Store>
-__device__ __forceinline__ void fft_pass(float2 w1, int tid, Load&& load, Store&& store) {
+__device__ __forceinline__ void fft_pass(float2 w1, float2 w8, int tid, Load&& load, Store&& store) {
   constexpr int NB = K / R;
   constexpr int B = (NB + NTH - 1) / NTH;
   static_assert(NS == 1 || B == 1, "twiddled passes: one butterfly per thread");
@@ -246,7 +265,8 @@ __device__ __forceinline__ void fft_pass(float2 w1, int tid, Load&& load, Store&
         float2 w = w1;
         static_for<1, R>([&](auto r) {
           v[b][r] = cmul(v[b][r], w);
-          if constexpr (r + 1 < R) w = cmul(w, w1);
+          if constexpr (R == 16 && r + 1 == 8) w = w8;
+          else if constexpr (r + 1 < R) w = cmul(w, w1);
         });
       }
       dft_nat<R>(v[b]);
@@ -281,6 +301,10 @@ struct StockhamChain<K, NTH, I, NS, PNS, PR, R, Rs...> {
     if constexpr (NS > 1) {
       if ((K / R) % NTH == 0 || t < K / R) w.w[I] = tw[(t & (NS - 1)) * (K / (NS * R))];
     }
+    w.h[I] = make_float2(1.f, 0.f);
+    if constexpr (NS > 1 && R == 16) {  // 8 (j mod NS) K / (16 NS) < K / 2
+      if ((K / R) % NTH == 0 || t < K / R) w.h[I] = tw[(t & (NS - 1)) * (K / (NS * 2))];
+    }
     Next::load_tw(tw, t, w);
   }
   template <bool FIRST, bool LAST, bool PP, class TW, class F, class G>
@@ -294,13 +318,13 @@ struct StockhamChain<K, NTH, I, NS, PNS, PR, R, Rs...> {
     // does not
     constexpr bool sync_mid = !in_global && !out_regs && !PP;
     if constexpr (in_global && out_regs)
-      fft_pass<K, R, NS, NTH, false>(w.w[I], t, first, last);
+      fft_pass<K, R, NS, NTH, false>(w.w[I], w.h[I], t, first, last);
     else if constexpr (in_global)
-      fft_pass<K, R, NS, NTH, false>(w.w[I], t, first, lds_store);
+      fft_pass<K, R, NS, NTH, false>(w.w[I], w.h[I], t, first, lds_store);
     else if constexpr (out_regs)
-      fft_pass<K, R, NS, NTH, false>(w.w[I], t, lds_load, last);
+      fft_pass<K, R, NS, NTH, false>(w.w[I], w.h[I], t, lds_load, last);
     else
-      fft_pass<K, R, NS, NTH, sync_mid>(w.w[I], t, lds_load, lds_store);
+      fft_pass<K, R, NS, NTH, sync_mid>(w.w[I], w.h[I], t, lds_load, lds_store);
     if constexpr (!out_regs) __syncthreads();  // results visible to the next pass / the caller
     Next::template run<FIRST, LAST, PP>(dst, PP ? buf : alt, w, t, first, last);
   }
@@ -317,7 +341,7 @@ struct StockhamChain<K, NTH, I, NS, PNS, PR, R, Rs...> {
 template <int K, int NTH, int... Rs>
 struct FFTPlan {
   using Chain = StockhamChain<K, NTH, 0, 1, 0, 1, Rs...>;
-  using Tw = TwReg<sizeof...(Rs)>;
+  using Tw = TwReg<sizeof...(Rs), radix16_passes<Rs...>()>;
   static constexpr int kPasses = sizeof...(Rs);
   static __device__ __forceinline__ Tw load_tw(const float2* __restrict__ tw, int t) {
     Tw w;

@@ -349,7 +349,6 @@ struct omega_ctx {
   int rf_sizes = 1 << 14;   // resolution sizes on the register-FFT kernel (bit log2 N): the 16384-point one
   std::map<std::pair<int, int>, float*> windows;  // (m, kind) -> device window
   std::map<int, float2*> rots;                     // m -> true-peak rotation table
-  std::map<std::pair<int, int>, float4*> wgens;     // (m, kind) -> WinGen table
   // the feature families' float64 tables (get_twiddles64 / get_window64 / get_savgol below), each under
   // (its kind, its two parameters). Entries are never evicted: the configured params (phase.p.tw,
   // tdetect.p.tw_*, basszoom.p.win, voice.p.sg, ...) hold these pointers between calls.

@@ -251,7 +251,6 @@ struct SpectraParams {
   const float* x;
   int64_t n, stride;       // frames of 2K samples at x + f * stride
   const float* win;        // [2K]
-  const float4* wgen;      // the window as a per-thread generator (WinGen, regfft.hpp)
   float* mag_out;          // [n, K+1] or nullptr
   // A10 (MAX op): bands [0, n_valid) of n_out, band i = max(mag[starts[i]:ends[i]]) * scale[i]
   int n_out, n_valid;

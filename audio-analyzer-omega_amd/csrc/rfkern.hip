@@ -433,21 +433,18 @@ __device__ __forceinline__ void spectra_rf_body(const SpectraParams& p) {
     cj0 = p.cgoff[t / kGrp];
     cj1 = p.cgoff[t / kGrp + 1];
   }
-  const WinGen wg(p.wgen, t);
   asm volatile("" ::: "memory");
   OMEGA_STAMP_RT(30);
   OMEGA_STAMP(0);
-  if (wg.c2 == 0.f) {  // (uniform: Hann, the cfg3 window)
-    static_for<0, 16>([&](auto r) {
-      const float2 a = x2[t + NTH * r], w = wg.template at<r, false>();
-      v[r] = make_float2(a.x * w.x, a.y * w.y);
-    });
-  } else {
-    static_for<0, 16>([&](auto r) {
-      const float2 a = x2[t + NTH * r], w = wg.template at<r>();
-      v[r] = make_float2(a.x * w.x, a.y * w.y);
-    });
-  }
+  // The window from its float32 table, the one the reference multiplies by. (Until tests/test_pow2_rfft_bins.py
+  // it was generated per thread by a cosine rotation, each value within ~2e-7 of the table: an absolute
+  // error, so a frame with its energy where the window is small came out wrong -- an impulse at sample 1
+  // under Hann, w = 1.5e-7, by 1.3 % in every bin, and one at the last sample not as zero.)
+  const float2* w2 = reinterpret_cast<const float2*>(p.win);
+  static_for<0, 16>([&](auto r) {
+    const float2 a = x2[t + NTH * r], w = w2[t + NTH * r];
+    v[r] = make_float2(a.x * w.x, a.y * w.y);
+  });
   OMEGA_STAMP(1);
   FFT::template run_half<true>(v, bf, t, w1, w2b, t2);
   OMEGA_STAMP(2);

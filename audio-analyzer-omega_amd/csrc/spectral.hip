@@ -90,6 +90,8 @@ __global__ __launch_bounds__(NTH, 2 * NTH / 256) void rfft_kernel(RfftParams p) 
     return make_float2(a.x * w.x, a.y * w.y);
   });
   const float2* __restrict__ twN = p.tw[ilog2(2 * K)];
+  // the conjugations of the untangle turn the zeros of an all-zero frame into -0: x + 0 is x, and +0 for -0
+  auto pz = [](float2 z) { return make_float2(z.x + 0.f, z.y + 0.f); };
   float2* cp = p.cplx ? reinterpret_cast<float2*>(p.cplx) + i * (K + 1) : nullptr;
   float* mp = p.mag ? p.mag + i * (K + 1) : nullptr;
   for (int k = tid; k < K / 2; k += NTH) {
@@ -99,14 +101,14 @@ __global__ __launch_bounds__(NTH, 2 * NTH / 256) void rfft_kernel(RfftParams p) 
       xk = make_float2(z.x + z.y, 0.f);
       xkk = make_float2(z.x - z.y, 0.f);
       const float2 xm = cconj(buf[FFT::out(K / 2)]);
-      if (cp) cp[K / 2] = xm;
+      if (cp) cp[K / 2] = pz(xm);
       if (mp) mp[K / 2] = cabs(xm);
     } else {
       untangle(buf[FFT::out(k)], buf[FFT::out(K - k)], twN[k], xk, xkk);
     }
     if (cp) {
-      cp[k] = xk;
-      cp[K - k] = xkk;
+      cp[k] = pz(xk);
+      cp[K - k] = pz(xkk);
     }
     if (mp) {
       mp[k] = cabs(xk);
@@ -138,8 +140,9 @@ __global__ __launch_bounds__(256) void combine_kernel(CombineParams p) {
 
 // Resolutions of fewer than 512 points (FFTConfig allows any power of two, multi_resolution_fft.py:39):
 // one 64-thread workgroup per channel-frame, the windowed frame in LDS, each bin a direct sum over
-// the N <= 256 samples with the N-point twiddle table (float32, like numpy's single-precision rfft),
-// then the same epilogue as mrfft_frame (weighted magnitudes, combine entries).
+// the N <= 256 samples with the float32 N-point twiddle table, accumulated in float64 (N float32 roundings in
+// a row put an on-bin tone's own bin 5.7e-7 off at 256 points, where numpy's single-precision rfft is exact:
+// tests/test_pow2_rfft_bins.py), then the same epilogue as mrfft_frame (weighted magnitudes, combine entries).
 constexpr int kSmallThreads = 64;
 __global__ __launch_bounds__(kSmallThreads) void mrfft_small_kernel(SpectralParams p, int r) {
   __shared__ float xs[256];
@@ -152,15 +155,15 @@ __global__ __launch_bounds__(kSmallThreads) void mrfft_small_kernel(SpectralPara
   __syncthreads();
   const float2* __restrict__ tw = p.tw[ilog2(N)];
   for (int k = t; k <= K; k += kSmallThreads) {
-    float re = 0.f, im = 0.f;
+    double re = 0.0, im = 0.0;
     int e = 0;
     for (int n = 0; n < N; ++n) {
       const float2 w = tw[e];
-      re = fmaf(xs[n], w.x, re);
-      im = fmaf(xs[n], w.y, im);
+      re = fma((double)xs[n], (double)w.x, re);
+      im = fma((double)xs[n], (double)w.y, im);
       e = (e + k) & (N - 1);
     }
-    mag[k] = sqrtf(re * re + im * im);
+    mag[k] = (float)sqrt(re * re + im * im);
   }
   __syncthreads();
   if (rp.mag_out) {

@@ -18,6 +18,9 @@ the oracle uses (oracle.omega_ref.window_f32): the device multiplies float32 by 
 so the window's own rounding is not counted against it. ``yardstick(frame, window)`` is the reference's own
 float32 path (oracle.omega_ref.gpu_fft; np.fft.rfft of the float32 product for `rect`), complex64, and
 ``deviation`` its distance from ``expect``: max_k |X32 - X64| / max_k |X64|.
+
+``designed_pow2`` / ``reference_pow2`` are the same for tests/test_pow2_rfft_bins.py, with the tones and the
+two-impulse frame the power-of-two kernels need on top (see there).
 """
 from __future__ import annotations
 
@@ -151,6 +154,87 @@ def deviation(X32, X64):
 def reference(n, window):
     """(X64 [F, n//2 + 1] complex128, dev [F]) of designed(n)'s frames under `window`, computed once."""
     _, _, frames = designed(n, window)
+    X = np.stack([expect(f, window) for f in frames])
+    dev = np.array([deviation(yardstick(f, window), x) for f, x in zip(frames, X)])
+    X.setflags(write=False)
+    dev.setflags(write=False)
+    return X, dev
+
+
+# ---- additions for the power-of-two kernels (tests/test_pow2_rfft_bins.py) ----
+
+REG_FFT_MIN = 8192  # the register FFT (regfft.hpp RegFFT<K>, K = n / 2 = 4096, 8192) serves these lengths
+PAIR_LEVEL = 0.5
+
+
+def pow2_tone_bins(n):
+    """On-bin tones beyond tone_bins(n) for n = 2K a power of two: the special slots of untangle and
+    rfft_magnitudes (bins 1, K/2 - 1, K/2, K/2 + 1, K - 1) and, where the register FFT runs (n >= 8192,
+    NTH = K / 16 threads, thread t owning the bins t + NTH q), the bins t + NTH q for q in {0, 7} and
+    t in {0, 63, 64, 255}: wave and round edges of the pair ownership. Bins past n / 2 or below 0 (tiny
+    n) are dropped, as are those tone_bins(n) already has."""
+    assert n >= 2 and n & (n - 1) == 0
+    K = n // 2
+    bins = {1, K // 2 - 1, K // 2, K // 2 + 1, K - 1}
+    if n >= REG_FFT_MIN:
+        nth = K // 16
+        bins |= {t + nth * q for q in (0, 7) for t in (0, 63, 64, 255)}
+    return sorted(b for b in bins if 0 <= b <= K and b not in tone_bins(n))
+
+
+def pair_positions(n):
+    """(a, b) of the `pair` frame: a = n // 3, b = a + an odd distance near n / 6."""
+    a = n // 3
+    return a, a + ((n // 6) | 1)
+
+
+def pair(n):
+    """Unit impulse at a plus PAIR_LEVEL at b: |X_k| = |w[a] + PAIR_LEVEL w[b] e^{-2 pi i k (b - a) / n}|
+    differs from bin to bin (between 0.5 and 1.5 under `rect`) and, b - a being odd, between k and
+    n / 2 - k: it tells the bins apart for the paths that emit magnitudes only, on which a single impulse
+    has the same magnitude in every bin."""
+    a, b = pair_positions(n)
+    assert a < b < n
+    x = np.zeros(n)
+    x[a] = 1.0
+    x[b] = PAIR_LEVEL
+    return x
+
+
+def pow2_signals64(n):
+    """signals64(n), the further tones of pow2_tone_bins(n) and the `pair` frame."""
+    out = signals64(n)
+    out += [(f"tone_{k0}", tone(n, k0)) for k0 in pow2_tone_bins(n)]
+    out.append(("pair", pair(n)))
+    return out
+
+
+def pow2_closed_form(name, n, window):
+    if name == "pair":
+        a, b = pair_positions(n)
+        k = np.arange(n // 2 + 1)
+        w = window64(n, window)
+        return w[a] * np.exp(-2j * np.pi * ((k * a) % n) / n) + PAIR_LEVEL * w[b] * np.exp(-2j * np.pi * ((k * b) % n) / n)
+    return closed_form(name, n, window)  # (tone_0 and a tone at n / 2: both exponentials land on one bin)
+
+
+@functools.lru_cache(maxsize=None)
+def designed_pow2(n, window="rect"):
+    """designed(n, window) over pow2_signals64(n): ([name...], {name: closed form or None}, float32 [F, n])."""
+    sig = pow2_signals64(n)
+    names = [s[0] for s in sig]
+    assert len(set(names)) == len(names)
+    closed = {nm: pow2_closed_form(nm, n, window) for nm in names}
+    frames = np.stack([s[1] for s in sig]).astype(np.float32)
+    frames.setflags(write=False)
+    return names, closed, frames
+
+
+@functools.lru_cache(maxsize=None)
+def reference_pow2(n, window):
+    """(X64 [F, n//2 + 1] complex128, dev [F]) of designed_pow2(n)'s frames under `window`, computed once
+    (dev = 0 for a frame whose windowed product is exactly zero)."""
+    _, _, frames = designed_pow2(n, window)
     X = np.stack([expect(f, window) for f in frames])
     dev = np.array([deviation(yardstick(f, window), x) for f, x in zip(frames, X)])
     X.setflags(write=False)

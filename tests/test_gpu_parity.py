@@ -49,6 +49,9 @@ def test_native_library_is_the_path():
 @pytest.mark.parametrize("name", ["sine1k_2048", "noise_2048", "triad_4096", "comp_4096", "silence_4096",
                                   "sine50_8192"])
 def test_mrfft_golden_default(mr, name):
+    """The default resolutions against the reference's golden magnitudes and combines. SPEC_TOL is the
+    north-star bar only: the float32-accuracy comparison of every resolution kernel, bin by bin on designed
+    signals, is tests/test_pow2_rfft_bins.py (eps32 log2(2N) at most)."""
     m = _mrfft()
     x = mr[f"{name}/x"]
     res = m.process_audio_chunk(x)
@@ -641,7 +644,9 @@ def test_chroma_genre_golden(golden, genre):
 def test_gpu_accelerated_fft_golden(golden):
     """GPUAcceleratedFFT facade: compute_fft per window and input dtype (float32 device transform vs
     the reference's CPU branch, 1e-4 normwise), its first-100-bytes cache, the multi-resolution
-    dict with a zero-padded size, process_fft_batch on device tensors, lengths of any factorization."""
+    dict with a zero-padded size, process_fft_batch on device tensors, lengths of any factorization. The
+    1e-4 is the north-star bar only: the float32-accuracy comparison, bin by bin on designed signals, is
+    tests/test_pow2_rfft_bins.py (powers of two 512..16384) and tests/test_any_rfft.py (other lengths)."""
     import torch
     from omega_gpu.gpu_accelerated_fft import GPUAcceleratedFFT
     g = golden("gpufft")
@@ -1379,7 +1384,9 @@ def test_spectra_cfg3_vs_oracle():
     """cfg3 fused analysis (omega_spectra): Hann rfft magnitude (A13) -> 512 log bands (A10) and the
     raw chromagram (A12) of alternating triad / noise frames, against the oracle chain. Tolerances:
     magnitudes 1e-4 normwise (north star), bands 1e-4 relative, chroma 1e-5 relative (float32
-    projection weights instead of the reference's float64 matrix)."""
+    projection weights instead of the reference's float64 matrix). The 1e-4 is the north-star bar only: the
+    float32-accuracy comparison of the magnitudes, bin by bin on designed signals, is
+    tests/test_pow2_rfft_bins.py (test_spectra_rf)."""
     from omega_gpu import Engine, Resolution
     from omega_gpu.engine import BandTable
     from omega_gpu import _lib as L
