@@ -42,6 +42,15 @@ inline int searchsorted_left_uniform(double step, int n_bins, double v) {
 inline double np_linspace0(int k, int num, double stop) {
   return k == num - 1 ? stop : (double)k * (stop / (double)(num - 1));
 }
+// np.linspace(start, stop, num)[k] as numpy evaluates it (num >= 2, stop != start): step = (stop - start) / (num - 1),
+// arange * step rounded, + start rounded (two roundings, never one fused), and the last point is stop itself
+inline double np_linspace(int k, int num, double start, double stop) {
+#pragma clang fp contract(off)
+  if (k == num - 1) return stop;
+  const double step = (stop - start) / (double)(num - 1);
+  const double prod = (double)k * step;
+  return prod + start;
+}
 // np.argmax(np.linspace(0, stop, num) >= v): the first such index, 0 where there is none
 inline int linspace0_argmax_ge(int num, double stop, double v) {
   for (int k = 0; k < num; ++k)

@@ -65,6 +65,8 @@ hipError_t launch_basszoom_track(const BassZoomParams& p, hipStream_t s);
 hipError_t launch_waterfall(const WaterfallParams& p, hipStream_t s);
 hipError_t launch_waterfall_colors(const WaterfallColorParams& p, hipStream_t s);
 hipError_t launch_tonal(const TonalParams& p, hipStream_t s);
+hipError_t launch_meterpanel_frames(const MeterPanelParams& p, int wave_max, hipStream_t s);
+hipError_t launch_meterpanel_track(const MeterPanelParams& p, bool walk, hipStream_t s);
 hipError_t launch_batch(const SpectralParams& sp, const KWeightParams& kp, const BatchPlan& bp, const MeterPrepParams& mp,
                         int grid, hipStream_t s);
 }  // namespace omega
@@ -207,6 +209,18 @@ struct TonalState {
   double* raw = nullptr;
   int64_t raw_cap = 0;
   double* chain[2] = {};
+};
+
+// capi_meterpanel.cpp -- the professional meters panel (omega_meterpanel_configure / omega_meterpanel_update): the
+// configured shape with the uploaded edges, the [hist_lo, hist_hi] pairs whose edges are in omega_ctx::tables, and
+// the frame kernel's per-call records (the panel's state travels with the caller)
+struct MeterPanelState {
+  bool set = false;
+  MeterPanelParams p{};
+  int64_t state_len = 0;
+  std::vector<std::pair<double, double>> ranges;
+  double* ws = nullptr;
+  int64_t ws_cap = 0;
 };
 
 // capi_features.cpp -- the stream state of a feature that compares each frame's spectrum with the one
@@ -388,6 +402,7 @@ struct omega_ctx {
   RhythmState rhythm;
   WaterfallState waterfall;
   TonalState tonal;
+  MeterPanelState meterpanel;
   // omega_weighting: float64 filter cascades per mode and the per-launch working buffers
   W64Stage* w64[4] = {};
   // frames of any length (anyfft.hip): per N the radices and the twiddle / rotation tables

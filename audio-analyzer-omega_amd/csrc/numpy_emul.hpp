@@ -92,7 +92,9 @@ __device__ __forceinline__ float np_leaf_combine(int n, const float* ls, int& id
 // so its recursion sees a contiguous array of n elements whatever lo is. np_emit_leaves lists the
 // recursion's leaves (depth-first) as off | len << 16 with off counted from `off`; np_slice_leaf sums one
 // leaf of term(i), i = 0 .. n - 1, in numpy's order (any lane, any leaf); np_leaf_combine<D>(n, ...) adds
-// the leaf sums. D = 7 covers n <= 16384.
+// the leaf sums. D = 7 covers every n <= 8192 and the n <= 16384 whose halves stay even enough (16384 itself, 4800);
+// numpy's halves are uneven (n2 = n / 2 - (n / 2) % 8), and a length such as 16383 goes 8199, 4103, ..., 263, 135 and
+// splits an eighth time: such lengths need D = 8 (meterpanel.hip runs these pieces with it).
 template <int D>
 __device__ __forceinline__ void np_emit_leaves(int off, int n, unsigned* tab, int& idx) {
   if constexpr (D == 0) {

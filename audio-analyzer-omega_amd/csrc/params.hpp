@@ -760,6 +760,47 @@ struct TonalParams {
   double* mode;             // [n_frames, 12, 7] or nullptr
 };
 
+// ProfessionalMetersPanel.update's own work (meterpanel.hip; omega4/panels/professional_meters.py:348-397, :568-579):
+// per frame the attack scan and the crest-factor operands in the frame's dtype, then one wave that carries the peak
+// hold, the transient values, the three histories and the level histogram over the call's frames in order
+constexpr int kMpThreads = 256;
+constexpr int kMpMaxFrame = 16384;   // np_rms_f32's range
+constexpr int kMpMaxLeaves = 256;    // numpy's pairwise leaves hold 64..128 elements above 128
+constexpr int kMpMaxHist = 4096;     // the cap of each history length
+constexpr int kMpMaxBins = 62;       // lanes 62 and 63 run the hold machine and the transient carry
+constexpr int kMpRowCols = 8;        // see include/omega.h for the columns
+constexpr int kMpWsCols = 5;         // per-frame record: attack count, first attack, max |x|, rms, non-finite flag
+// the state blob: kMpHead values, then the level, true-peak and range rings
+enum MpState : int { kMpHold = 0, kMpCounter, kMpAttack, kMpPunch, kMpCount, kMpLevelFill, kMpLevelPos, kMpPeakFill,
+                     kMpPeakPos, kMpRangeFill, kMpRangePos, kMpHead = 16 };
+enum MpFlag : int { kMpFlagAttack = 1, kMpFlagNonFinite = 2 };
+#ifndef OMEGA_MP_WAVE_MAX            // frames up to this length take one wave each, four to a workgroup
+#define OMEGA_MP_WAVE_MAX 2048
+#endif
+constexpr int kMpWaveMax = OMEGA_MP_WAVE_MAX;
+constexpr int kMpHistChunk = 256;    // frames per workgroup of the prefix-count histogram kernel
+#ifdef OMEGA_MP_TRACK_WALK           // builds the measured alternative: the histogram walked by the track kernel's wave
+constexpr bool kMpTrackWalk = true;
+#else
+constexpr bool kMpTrackWalk = false;
+#endif
+struct MeterPanelParams {
+  Rows frames;              // frame_len samples per frame
+  int64_t n_frames;
+  int frame_len;
+  double sample_rate;
+  int level_len, peak_len, range_len, n_bins;
+  const double* edges;      // [n_bins + 1] np.linspace(hist_lo, hist_hi, n_bins + 1)
+  const double* meters;     // [n_frames, 5] momentary, short_term, integrated, range, true_peak
+  int64_t hold_samples;     // peak_hold_samples
+  int reset_hold;           // reset_peak_hold before the first frame
+  double* ws;               // [n_frames, kMpWsCols] the frame kernel's records
+  const double* state_in;   // [kMpHead + level_len + peak_len + range_len] or nullptr (a new panel)
+  double* state_out;        // the same, or nullptr
+  double* rows;             // [n_frames, kMpRowCols]
+  int32_t* hist;            // [n_frames, n_bins] or nullptr
+};
+
 // Frames of any length (anyfft.hip): mixed-radix Stockham transform, true peak and windowed rfft
 constexpr int kAnyMaxStages = 32;
 constexpr int kAnyLdsMax = 6826;  // 3 N float2 in 160 KiB of LDS; above: global scratch

@@ -20,12 +20,13 @@ from .frequency_band_tracker import FrequencyBandTracker, FrequencyBandTrackerPa
 from .spectrogram_waterfall import SpectrogramWaterfall, SpectrogramWaterfallPanel
 from .chromagram import ChromagramAnalyzer, ChromagramPanel
 from .music_theory import MusicTheory
+from .professional_meters import ProfessionalMetersPanel
 
 __all__ = [
     "SpectrogramWaterfall", "SpectrogramWaterfallPanel", "ChromagramAnalyzer", "ChromagramPanel", "MusicTheory",
     "HarmonicAnalyzer", "HarmonicMetrics", "GenreClassifier", "HipHopDetector", "PhaseCorrelation",
     "RoomModeAnalyzer", "RoomModeConfig", "VoiceDetectionPanel", "TransientDetectionPanel", "BassZoomPanel",
-    "BeatDetector", "BeatDetectionPanel", "FrequencyBandTracker", "FrequencyBandTrackerPanel",
+    "ProfessionalMetersPanel", "BeatDetector", "BeatDetectionPanel", "FrequencyBandTracker", "FrequencyBandTrackerPanel",
     "LIB_PATH", "OmegaError", "UnsupportedError", "lib", "Engine", "Resolution", "BandTable",
     "DEFAULT_RESOLUTIONS", "NORTHSTAR_RESOLUTIONS", "METER_KEYS",
     "CepstralAnalyzer", "PitchDetectionConfig", "get_preset_config", "list_presets",

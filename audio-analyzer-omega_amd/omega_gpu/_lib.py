@@ -101,6 +101,12 @@ class TonalConfig(C.Structure):
     _fields_ = [("genre", C.c_int32)]
 
 
+class MeterPanelConfig(C.Structure):
+    _fields_ = [("sample_rate", C.c_double), ("frame_len", C.c_int32), ("level_len", C.c_int32),
+                ("peak_len", C.c_int32), ("range_len", C.c_int32), ("n_bins", C.c_int32), ("hist_lo", C.c_double),
+                ("hist_hi", C.c_double)]
+
+
 FMT = {"float32le": 0, "s16le": 1}
 INGEST_COMBINED, INGEST_LUFS, INGEST_TRUE_PEAK, INGEST_METERS = 1, 2, 4, 8
 
@@ -203,6 +209,13 @@ EXPORTS = {
     "omega_tonal_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 9 + [C.c_int]),
     "omega_tonal_spectra": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_double] + [C.c_void_p] * 9
                             + [C.c_int]),
+    "omega_meterpanel_config_default": (None, [C.POINTER(MeterPanelConfig)]),
+    "omega_meterpanel_state_size": (C.c_int64, [C.POINTER(MeterPanelConfig)]),
+    "omega_meterpanel_edges": (C.c_int, [C.POINTER(MeterPanelConfig), C.c_void_p]),
+    "omega_meterpanel_unpack": (C.c_int, [C.POINTER(MeterPanelConfig)] + [C.c_void_p] * 9),
+    "omega_meterpanel_configure": (C.c_int, [C.c_void_p, C.POINTER(MeterPanelConfig)]),
+    "omega_meterpanel_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                          C.c_int64, C.c_int32] + [C.c_void_p] * 4 + [C.c_int]),
     "omega_ingest_config_default": (None, [C.POINTER(IngestConfig)]),
     "omega_ingest_create": (C.c_int, [C.c_void_p, C.POINTER(IngestConfig), C.POINTER(C.c_void_p)]),
     "omega_ingest_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

@@ -997,6 +997,71 @@ int omega_tonal_spectra(omega_ctx* ctx, const float* spectra, int64_t n_frames, 
                         const int32_t* roll, const int32_t* first, const double* state_in, double* state_out,
                         double* rows, double* key_corr, double* alt_corr, double* chord, double* mode, int mem);
 
+/* ProfessionalMetersPanel.update (omega4/panels/professional_meters.py:348-397, with :554-579) for consecutive frames
+ * of one stream: what the panel does with a frame and with the five values calculate_lufs returned for it -- the
+ * level, true-peak and loudness-range histories, the level histogram, the peak hold and the "simple transient
+ * detection". The metering itself is omega_calculate_lufs; its meters rows are this call's input. The context keeps
+ * only the configured shape; the caller carries the panel's state, omega_meterpanel_state_size(cfg) float64 values:
+ *   0 hold value, 1 hold counter, 2 attack_time, 3 punch_factor, 4 transients_detected, 5 / 6 the level ring's fill
+ *   and next slot, 7 / 8 the true-peak ring's, 9 / 10 the range ring's, 11..15 zero, then the three rings (level_len,
+ *   peak_len, range_len values; a ring fills from slot 0 and then wraps)
+ * from state_out of one call to state_in of the next. state_in NULL: a new panel (hold -100 / 0, transient values 0,
+ * empty histories). state_out NULL: not wanted. Both live where `mem` says and may be the same buffer. One call on F
+ * frames equals F one-frame calls chained through the blob, bit for bit; n_frames 0 writes state_in's panel (with
+ * reset_hold applied) to state_out. The entry points are additive to ABI 5.
+ * omega_meterpanel_state_size, omega_meterpanel_edges and omega_meterpanel_unpack need no context and no device.
+ * They, and omega_meterpanel_configure, return OMEGA_EINVAL for a sample rate that is not positive and finite, a
+ * negative frame_len, a history length outside 1..OMEGA_METERPANEL_MAX_HISTORY, n_bins outside
+ * 1..OMEGA_METERPANEL_MAX_BINS, hist_lo / hist_hi not finite or not increasing (or so close that two edges
+ * coincide), and OMEGA_EUNSUP for frame_len 0 or above OMEGA_METERPANEL_MAX_FRAME; a refused configure leaves the
+ * configured shape as it was. omega_meterpanel_edges writes the n_bins + 1 histogram edges, np.linspace(hist_lo,
+ * hist_hi, n_bins + 1) as numpy evaluates it; the device searches this very table. omega_meterpanel_unpack reads a
+ * blob in host memory: the three histories oldest first (level_len / peak_len / range_len values of room each) with
+ * their lengths, hold[2] = value, counter and transient[3] = attack_time, punch_factor, transients_detected; every
+ * output may be NULL; a blob whose fills and slots are not a ring's returns OMEGA_EINVAL and writes nothing.
+ * omega_meterpanel_update: frame f has its frame_len samples (float32, or float64 when f64) at frames +
+ * f*frame_stride, in elements; rows may overlap. meters [n_frames, 5] float64 as omega_calculate_lufs writes them
+ * (momentary, short_term, integrated, range, true_peak). peak_hold_samples is the panel's attribute at these frames;
+ * reset_hold non-zero applies reset_peak_hold before the first frame. Per frame, in order: the histories take
+ * momentary, range and true_peak; the hold takes true_peak and the counter peak_hold_samples where true_peak > hold,
+ * else the counter drops by one and at <= 0 the hold takes true_peak (the counter runs negative without bound); and,
+ * in the frame's dtype, d = diff(|x|): where any d > 0.1 (float32 frames: against float32(0.1)), attack_time =
+ * (first such index / sample_rate) * 1000, punch_factor = max|x| / sqrt(mean(x^2)) with numpy's pairwise sum and a
+ * correctly rounded divide (0 unless the rms is > 0), transients_detected = their number; where none, the three keep
+ * the frame before's. NaN follows numpy: np.max propagates it and every comparison with it is false.
+ *   rows [n_frames, OMEGA_METERPANEL_COLS] float64:
+ *     0 hold value   1 hold counter   2 attack_time in ms   3 punch_factor   4 transients_detected
+ *     5 flags: bit 0 an attack in this frame, bit 1 a non-finite sample in it
+ *     6 the level history's fill   7 the histogram's sum
+ *   hist [n_frames, n_bins] int32 or NULL: np.histogram(level_history, edges) after frame f -- bin b holds
+ *     edges[b] <= v < edges[b + 1], the last bin also v == edges[n_bins], every other value (NaN, -100) nowhere
+ * Float32 frames give numpy's bits in every column; float64 frames differ from numpy in the punch factor alone, by
+ * the rounding of the square root and the divide (1e-12 relative at the very most). */
+#define OMEGA_METERPANEL_COLS 8
+#define OMEGA_METERPANEL_MAX_BINS 62
+#define OMEGA_METERPANEL_MAX_HISTORY 4096
+#define OMEGA_METERPANEL_MAX_FRAME 16384
+typedef struct {
+  double sample_rate;
+  int32_t frame_len;   /* samples per audio frame, 1..16384 (1: the meters part only, as the reference's len > 1) */
+  int32_t level_len;   /* level_history's maxlen */
+  int32_t peak_len;    /* true_peak_history's */
+  int32_t range_len;   /* loudness_range_history's */
+  int32_t n_bins;      /* histogram bins */
+  double hist_lo, hist_hi;
+} omega_meterpanel_config;
+/* 48000 Hz, 2048 samples, 600 / 300 / 300, 60 bins over -60..0. */
+void omega_meterpanel_config_default(omega_meterpanel_config* cfg);
+int64_t omega_meterpanel_state_size(const omega_meterpanel_config* cfg);
+int omega_meterpanel_edges(const omega_meterpanel_config* cfg, double* out);
+int omega_meterpanel_unpack(const omega_meterpanel_config* cfg, const double* state, double* level, int32_t* n_level,
+                            double* peaks, int32_t* n_peaks, double* ranges, int32_t* n_ranges, double* hold,
+                            double* transient);
+int omega_meterpanel_configure(omega_ctx* ctx, const omega_meterpanel_config* cfg);
+int omega_meterpanel_update(omega_ctx* ctx, const void* frames, int64_t frame_stride, int32_t f64, const double* meters,
+                            int64_t n_frames, int64_t peak_hold_samples, int32_t reset_hold, const double* state_in,
+                            double* rows, int32_t* hist, double* state_out, int mem);
+
 /* ---- Sustained-stream ingest ------------------------------------------
  * The capture byte stream of omega4/audio/capture.py:546-600 (parec float32le / s16le, fixed chunks
  * of chunk_size samples, s16 scaled by 1/32768), its per-chunk noise gate (:620-641: RMS, background

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Run one stage of the cfg2 hot path in isolation (for rocprofv3 counter passes and A/B timing).
 
-  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre,room,voice,waterfall,tonal} [--reps N]
+  python tools/kernel_bench.py {batch,tp,kw,mrfft,meters,all,host,spectra,drums,post,pitch,harmonic,genre,room,voice,waterfall,tonal,meterpanel} [--reps N]
 
 spectra-bands / spectra-chroma / spectra-mag: the cfg3 kernel with one output set only (where its LDS
 bank conflicts and time come from); spectra-rot: bench.py's cfg3 call, rotating over 4 distinct input
@@ -14,6 +14,8 @@ waterfall: omega_waterfall_rows over 4096 resident frames (1025 bins, 853 cells;
 the RGB output) and omega_waterfall_colors over a 200 x 853 history; with --lib, another build of the same ABI.
 tonal: omega_tonal_features over 4096 resident chroma rows and omega_tonal_spectra over 4096 resident spectra of 4097
 bins, rows only and with the four detail matrices; with --lib, a build with another OMEGA_TONAL_LANES.
+meterpanel: omega_meterpanel_update on resident float64 frames at 2048, 16384, 256 and 1 samples (1, 256 and 4096
+frames); --samples and --frames pick one shape; with --lib, a build of the measured alternatives (make alt).
 """
 import argparse
 import os
@@ -217,12 +219,69 @@ def tonal(reps):
     print("tonal row 0:", rows[0, 12:28].cpu().numpy())
 
 
+def meterpanel(reps, samples=None, frames=None):
+    """omega_meterpanel_update (its kernels behind one another) on resident float64 frames and meters: the app's shape
+    (2048 samples; 1 and 4096 frames), 16384 samples, 256 samples, and 1-sample frames, where the frame kernel has
+    nothing to do. With --samples M --frames F that one shape alone, for a kernel-trace run that splits the call
+    into its kernels; with --lib, a build of the measured alternatives (`make alt`). Three passes of `reps`
+    calls each between one event pair; the median pass, per call."""
+    import ctypes as C
+    from omega_gpu import ProfessionalMetersPanel
+    from omega_gpu import _lib as L
+    lib = L.lib()
+    rng = np.random.default_rng(15)
+    p = ProfessionalMetersPanel(48000)
+    eng = p._eng
+    Fmax = 4096
+    meters = np.zeros((Fmax, 5))
+    meters[:, 0] = rng.uniform(-70, 3, Fmax)
+    meters[:, 3] = rng.uniform(0, 12, Fmax)
+    meters[:, 4] = rng.uniform(-20, 0, Fmax)
+    meters = torch.from_numpy(meters).cuda()
+    rows = torch.empty(Fmax, 8, dtype=torch.float64, device="cuda")
+    hist = torch.empty(Fmax, 60, dtype=torch.int32, device="cuda")
+    state = torch.zeros(p._state_len, dtype=torch.float64, device="cuda")
+    eng._bind_stream(meters)
+
+    def timed(m, F):
+        cfg = L.MeterPanelConfig.from_buffer_copy(p._cfg)
+        cfg.frame_len = m
+        eng._check(lib.omega_meterpanel_configure(eng._ctx, C.byref(cfg)))
+        x = torch.from_numpy(0.3 * rng.standard_normal((F, m))).cuda()
+
+        def call():
+            eng._check(lib.omega_meterpanel_update(eng._ctx, x.data_ptr(), m, 1, meters.data_ptr(), F, 60, 0, None,
+                                                   rows.data_ptr(), hist.data_ptr(), state.data_ptr(), L.MEM_DEVICE))
+        for _ in range(5):
+            call()
+        torch.cuda.synchronize()
+        passes = []
+        for _ in range(3):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(reps):
+                call()
+            e.record()
+            e.synchronize()
+            passes.append(s.elapsed_time(e) * 1e3 / reps)
+        med = float(np.median(passes))
+        print(f"meterpanel {m} samples x {F} frames: median {med:.1f} us per call "
+              f"(passes {', '.join(f'{v:.1f}' for v in passes)}); {med / F * 1e3:.1f} ns per frame")
+
+    shapes = [(samples, frames)] if samples else ((2048, 1), (2048, 4096), (16384, 1), (16384, 256), (256, 4096),
+                                                   (1, 1), (1, 4096))
+    for m, F in shapes:
+        timed(m, min(F, Fmax))
+    print("meterpanel row 0:", rows[0].cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("stage")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--frames", type=int, default=256, help="stereo frames per call (cfg2: 256, cfg4 shard: 4096)")
     ap.add_argument("--bins", type=int, default=512, help="genre: spectrum bins per frame (512, 4097)")
+    ap.add_argument("--samples", type=int, default=None, help="meterpanel: this frame length with --frames alone")
     ap.add_argument("--lib", default=None, help="another build in lib/ (A/B of two builds on one box)")
     a = ap.parse_args()
     if a.lib:
@@ -236,6 +295,8 @@ def main():
         return waterfall(a.reps)
     if a.stage == "tonal":
         return tonal(a.reps)
+    if a.stage == "meterpanel":
+        return meterpanel(a.reps, a.samples, a.frames)
     import bench
     from omega_gpu import NORTHSTAR_RESOLUTIONS, Engine
     from omega_gpu import _lib as L
